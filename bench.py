@@ -1,11 +1,16 @@
 #!/usr/bin/env python
 """Benchmark of the MAPPO hot path: env-steps/sec through GAE + ppo_update.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns|cfg2|cfg3|ns_rnn|smac|hanabi] [--no-cpu-baseline]
-                    [--matrix-arithmetic six_term|f32_mfma] [--no-f32-mfma] [--no-workloads]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ns|cfg2|cfg3|ns_rnn|smac|hanabi] [--full]
+                    [--dump-outputs DIR] [--no-cpu-baseline] [--matrix-arithmetic six_term|f32_mfma] [--no-f32-mfma]
+                    [--no-workloads]
 
-The default command line (north star, one GPU) also carries `workloads`: the other BASELINE.json configs run for three
-steps each by child processes of this script after the timed region (OTHER_WORKLOADS below; outside `value`).
+A plain run sets up, warms up, times K steps and prints the line: `value`, `ms_per_step` and the configuration.
+``--full`` adds everything else below -- per-launch timings and rooflines (event pairs inside the timed steps), the
+collective timings, the step under the other arithmetic form, the CPU leg, and on the north star with one GPU
+`workloads`: the other BASELINE.json configs run for a few steps each by child processes of this script after the timed
+region (OTHER_WORKLOADS below; outside `value`).  ``--dump-outputs DIR`` writes what the last timed step computed as
+DIR/<name>.npy (snapshot_outputs); the inputs are seeded, so two builds can be compared output for output.
 
 One "step" = one pass of the hot path over one synthetic rollout that is already resident in HBM:
 ``buffer.compute_returns`` (HIP GAE scan) + ``R_MAPPO.train`` (ppo_epoch x num_mini_batch fused
@@ -291,7 +296,7 @@ def other_workloads(opt, budget_s):
             res[name] = {"what": what, "skipped": "the leg's time budget (%d s) was spent" % budget_s}
             continue
         cmd = [sys.executable, os.path.abspath(__file__)] + argv + [
-            "--steps", str(k_steps), "--warmup", str(k_warm), "--no-f32-mfma", "--no-workloads", "--sampler-rng", opt.sampler_rng,
+            "--steps", str(k_steps), "--warmup", str(k_warm), "--full", "--no-f32-mfma", "--no-workloads", "--sampler-rng", opt.sampler_rng,
             "--matrix-arithmetic", opt.matrix_arithmetic] + (["--no-gemm-tuning"] if opt.no_gemm_tuning else [])
         if opt.no_cpu_baseline and "--no-cpu-baseline" not in cmd:
             cmd.append("--no-cpu-baseline")
@@ -312,6 +317,42 @@ def other_workloads(opt, budget_s):
     if res.get("smac_shard64") and res.get("smac") and "cpu_baseline" in res["smac_shard64"]:
         res["smac_shard64"]["cpu_baseline"] = res["smac"].get("cpu_baseline")
     return res
+
+
+DUMP_MAX_ELEMENTS = 1 << 20       # per array; a larger output is dumped as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def snapshot_outputs(buf, policy, trainer, info):
+    """What a caller of the timed path holds after its last step, copied to the host: the returns of the GAE scan, the
+    updated actor / critic weights, the value normaliser's moments and train()'s statistics -> {name: float32 / float64
+    array}.  An array of more than DUMP_MAX_ELEMENTS elements keeps the elements at a seeded random choice of flat indices
+    (seeded by its size, so two runs with the same arguments keep the same ones)."""
+    def host(t):
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            rng = np.random.default_rng(t.numel())
+            idx = np.sort(rng.choice(t.numel(), DUMP_MAX_ELEMENTS, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        return a if a.dtype == np.float64 else a.astype(np.float32)
+
+    out = {"returns": host(buf.returns)}
+    for prefix, module in (("actor", policy.actor), ("critic", policy.critic), ("value_normalizer", trainer.value_normalizer)):
+        if isinstance(module, torch.nn.Module):
+            for k, v in module.state_dict().items():
+                out["%s.%s" % (prefix, k)] = host(v)
+    for k, v in info.items():
+        out["train_info.%s" % k] = np.asarray(float(v), np.float64)
+    return out
+
+
+def write_outputs(d, outputs):
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= DUMP_MAX_BYTES, "outputs of %d bytes exceed the %d-byte budget" % (total, DUMP_MAX_BYTES)
+    os.makedirs(d, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def self_launch(n_gpus):
@@ -349,6 +390,12 @@ def main():
                     help="narrow buffers take the time-parallel GAE scan (--gae_scan: ~1e-6 relative instead of bit-exact)")
     ap.add_argument("--no-gemm-tuning", action="store_true",
                     help="leave GEMM kernel selection to the library heuristic (onpolicy/utils/gemm_tuning.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: per-launch timings and rooflines, the other arithmetic "
+                         "form, the CPU leg, the collective timings and (north star, one GPU) the other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (returns, updated weights, value normaliser, train_info) "
+                         "as DIR/<name>.npy")
     opt = ap.parse_args()
 
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -416,10 +463,13 @@ def main():
         step()      # untimed: any GEMM shape without a stored winner is tuned here, never in the timed region
     for _ in range(opt.warmup):
         step()
-    buf.profile_kernels(True)
     from onpolicy.algorithms.utils import fused_mlp
-    fused_mlp.profile(True)
-    trainer.dp.time_collectives(True)
+    if opt.full:
+        # per-launch event pairs in the timed steps (the roofline objects, the collective timings); a plain run times the
+        # steps alone
+        buf.profile_kernels(True)
+        fused_mlp.profile(True)
+        trainer.dp.time_collectives(True)
     scalar0, reused0 = trainer.dp.scalar_collectives, trainer.dp.scales_reused
     replays0 = getattr(getattr(trainer, "_update_graph", None), "replays", 0)
     # Python's cyclic collector: a full collection walks every object alive (modules, fixtures of the process, ...) and fell
@@ -435,6 +485,8 @@ def main():
         info = step()
     fence()
     elapsed = time.perf_counter() - t0
+    # what the last timed step computed, before anything below (the --full legs) runs further steps on the same state
+    outputs = snapshot_outputs(buf, policy, trainer, info) if opt.dump_outputs and rank == 0 else None
     kt = buf.kernel_times()
     mt = fused_mlp.profile_times()
     n_coll, coll_ms, coll_bytes = trainer.dp.collective_times()
@@ -451,7 +503,7 @@ def main():
     # critic on two streams (R_MAPPOPolicy.evaluate_logits): a launch that shares the chip with the other network's cannot be
     # set against a roofline.  In both cases the launches are timed one after the other in the extra step.
     two_streams = bool(getattr(policy, "_side_streams", None))
-    if (ug is not None and ug.replays > 0 and not mt) or two_streams:
+    if opt.full and ((ug is not None and ug.replays > 0 and not mt) or two_streams):
         if ug is not None:
             ug.off = True
         two = os.environ.get("MAPPO_TWO_STREAM_UPDATE")
@@ -475,15 +527,17 @@ def main():
     # previous launch left them) -- reported next to the in-situ figure as roofline_gae.back_to_back
     buf.profile_kernels(False)
     reps = 10
-    buf.compute_returns(next_value, trainer.value_normalizer)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda._sleep(250000)
-    e0.record()
-    for _ in range(reps):
+    gae_b2b_ms = None
+    if opt.full:
         buf.compute_returns(next_value, trainer.value_normalizer)
-    e1.record()
-    torch.cuda.synchronize(dev)
-    gae_b2b_ms = e0.elapsed_time(e1) / reps
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda._sleep(250000)
+        e0.record()
+        for _ in range(reps):
+            buf.compute_returns(next_value, trainer.value_normalizer)
+        e1.record()
+        torch.cuda.synchronize(dev)
+        gae_b2b_ms = e0.elapsed_time(e1) / reps
     from onpolicy import _native
     gae_variant, buf_gae_exact = _native.lib().mappo_gae_last_variant(), buf._gae_exact
     # Outside the contract's timed region, next to `value`: the same step under the OTHER arithmetic form of the K9 / K12 matrix
@@ -493,7 +547,7 @@ def main():
     # same run.
     other = None
     other_name = "f32_mfma" if opt.matrix_arithmetic == "six_term" else "six_term"
-    if not opt.no_other_arithmetic and args.hidden_size in (64, 512):
+    if opt.full and not opt.no_other_arithmetic and args.hidden_size in (64, 512):
         policy.set_matrix_arithmetic(other_name)
         # (no tuning of GEMM shapes the shipped table does not hold in this leg: under f32_mfma a hidden-512 shard with an
         # unseen row count sent TunableOp into minutes of benchmarking -- unseen shapes take the library's heuristic pick here)
@@ -613,9 +667,12 @@ def main():
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             # how the float32 matrix products of K9 / K12 were formed in the timed region (inputs, outputs, accumulation and
             # every other operation are float32 either way)
+            # (hidden 512: whether K15 ran is read from its launch record, which only --full takes)
             "arithmetic": ARITHMETIC_TEXT[opt.matrix_arithmetic] if (args.hidden_size == 64 or (
                 args.hidden_size == 512 and opt.matrix_arithmetic == "six_term" and "mappo_linear512_forward" in mt)) else
-                          "f32 (library float32 GEMMs + K6 / K7)",
+                          "f32 (library float32 GEMMs + K6 / K7)" if (opt.full or args.hidden_size != 512 or
+                                                                    opt.matrix_arithmetic != "six_term") else
+                          ARITHMETIC_TEXT["six_term"] + " where K15 ran, else library float32 GEMMs + K6 / K7 (--full tells)",
             "hbm_peak_bytes_per_rank": peak_mem,
             "csrc_digest": here,        # of the kernel sources this run was built from (cf. roofline.traffic_csrc_digest)
             # updates of the timed region that were replays of a captured HIP graph (0: every update ran eagerly)
@@ -656,7 +713,12 @@ def main():
         }
         if other is not None:
             out[other_name] = other
-        g = out["roofline_gae"]
+        if not opt.full:
+            # the per-launch figures and the collective timings come from event pairs that only --full records
+            for k in ("roofline", "roofline_linear512_wgrad", "roofline_mlp_backward", "roofline_gae", "roofline_gather",
+                      "grad_allreduce"):
+                del out[k]
+        g = out.get("roofline_gae")
         if g is not None:
             # `frac` / `launch_ms` are the in-situ figures (first launch of a step, right behind the previous step's update);
             # back to back the same launch finds part of its lines in the Infinity Cache and warm TLBs
@@ -686,7 +748,7 @@ def main():
             g["back_to_back"] = {"launch_ms": round(gae_b2b_ms, 5), "launches": reps,
                                  "achieved": round(nbytes / (gae_b2b_ms * 1e-3) / 1e9, 1),
                                  "frac": round(nbytes / (gae_b2b_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-        if world == 1 and not opt.no_cpu_baseline:
+        if opt.full and world == 1 and not opt.no_cpu_baseline:
             cb = out["cpu_baseline"] = cpu_baseline(wl)
             ref = reference_recorded(opt.workload)
             factor = None
@@ -709,7 +771,7 @@ def main():
                 cb["reference_recorded"] = ref
     else:
         out = None
-    if out is not None and world == 1 and opt.workload == "ns" and not opt.threads and not opt.no_workloads:
+    if opt.full and out is not None and world == 1 and opt.workload == "ns" and not opt.threads and not opt.no_workloads:
         # the other BASELINE configs, by this same command line (outside `value`): hand the GPU over first
         del step, buf, trainer, policy, next_value, ug, info, kt, mt
         import gc
@@ -719,6 +781,8 @@ def main():
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
+    if outputs is not None:
+        write_outputs(opt.dump_outputs, outputs)
     if out is not None:
         # RCCL writes a version banner to the C stdio stream; push that out first so that the JSON
         # line is the LAST line this process prints

@@ -54,14 +54,18 @@ def inputs(spec, z, key):
 
 def start_from_reference_weights(policy, z, key, rtol=1e-4, atol=5e-6):
     """Same seed => the reference's initial weights up to the host LAPACK's last bits (orthogonal_'s QR); the update then
-    starts from the fixture's exact values."""
+    starts from the fixture's exact values.  ``atol`` holds for QRs of up to 64 reflections; the float32 rounding of a QR
+    grows with its number of reflections (the smaller side of the weight), and which bits it lands on depends on the host's
+    thread count and instruction set (hidden 512: up to 1.6e-5 between thread counts of one host), so a wider weight gets
+    ``atol`` scaled by that count / 64."""
     for net, pre in ((policy.actor, "init_actor."), (policy.critic, "init_critic.")):
         sd = net.state_dict()
         keys = [k[len(key + pre):] for k in z.files if k.startswith(key + pre)]
         assert sorted(keys) == sorted(sd.keys())
         for k, v in sd.items():
             ref = z[key + pre + k]
-            np.testing.assert_allclose(v.cpu().numpy(), ref, rtol=rtol, atol=atol, err_msg=pre + k)
+            qr_atol = atol * max(1.0, min(v.shape) / 64.0) if v.dim() == 2 else atol
+            np.testing.assert_allclose(v.cpu().numpy(), ref, rtol=rtol, atol=qr_atol, err_msg=pre + k)
             v.copy_(torch.from_numpy(ref))
 
 

@@ -57,3 +57,30 @@ def test_committed_line_carries_its_workloads_and_provenance():
     assert pmc["_provenance"]["csrc_digest"] == b.csrc_digest() == ns["csrc_digest"]
     rec = b.reference_recorded("ns")
     assert rec["source"].startswith("profiles/r06_cpu_port_vs_reference.json") and len(rec["port_vs_reference_same_machine"]) == 2
+
+
+def test_dumped_outputs_are_float_sampled_and_repeatable(tmp_path):
+    """--dump-outputs: float32 / float64 arrays only, an output above the element cap becomes the same seeded sample on
+    every call, and the files stay within the 64 MB budget."""
+    import numpy as np
+    import torch
+    b = _bench()
+
+    class Buf(object):
+        returns = torch.arange(3 * b.DUMP_MAX_ELEMENTS, dtype=torch.float32).reshape(3, -1, 1)
+
+    class Policy(object):
+        actor, critic = torch.nn.Linear(4, 3), torch.nn.Sequential(torch.nn.Linear(5, 1), torch.nn.BatchNorm1d(1))
+
+    class Trainer(object):
+        value_normalizer = None
+
+    one = b.snapshot_outputs(Buf(), Policy(), Trainer(), {"value_loss": 0.5})
+    two = b.snapshot_outputs(Buf(), Policy(), Trainer(), {"value_loss": 0.5})
+    assert one["returns"].shape == (b.DUMP_MAX_ELEMENTS,) and np.array_equal(one["returns"], two["returns"])
+    assert np.all(np.diff(one["returns"]) > 0)          # distinct elements, in storage order
+    assert all(a.dtype in (np.float32, np.float64) for a in one.values())
+    assert "critic.1.num_batches_tracked" in one and float(one["train_info.value_loss"]) == 0.5
+    b.write_outputs(str(tmp_path), one)
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(k + ".npy" for k in one)
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= b.DUMP_MAX_BYTES

@@ -18,7 +18,7 @@ def _run(extra_env=None, args=()):
     env.update(extra_env or {})
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--threads", "64", "--steps", "1",
-                          "--warmup", "1", "--no-cpu-baseline", "--sampler-rng", "host"]
+                          "--warmup", "1", "--full", "--no-cpu-baseline", "--sampler-rng", "host"]
                          + ([] if "--gemm-tuning" in args else ["--no-gemm-tuning"])
                          + [a for a in args if a != "--gemm-tuning"],
                          capture_output=True, text=True, env=env, timeout=600)
@@ -28,12 +28,12 @@ def _run(extra_env=None, args=()):
 
 
 def test_default_command_line_carries_the_other_baseline_configs():
-    """`python bench.py` (north star, one GPU) appends `workloads`: the other BASELINE configs run by child processes of the same
+    """`python bench.py --full` (north star, one GPU) appends `workloads`: the other BASELINE configs run by child processes of the same
     script after the timed region (VERDICT r5 "next" #1).  Here with two of the six (MAPPO_BENCH_WORKLOADS) to keep the test
     short: entries carry value / ms_per_step / arithmetic / the dominant launch against its roof / the GAE launch in situ."""
     env = dict(os.environ, MAPPO_BENCH_WORKLOADS="cfg2,smac_shard64", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-                          "--no-f32-mfma"], capture_output=True, text=True, env=env, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--full",
+                          "--no-cpu-baseline", "--no-f32-mfma"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                      # ONE JSON line, whatever the children printed
@@ -96,6 +96,37 @@ def test_bench_contract_and_rccl_single_rank():
         assert forced["train_info"][k] == pytest.approx(v, rel=2e-3, abs=1e-5), k
 
 
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline figures and none of the per-launch ones; --dump-outputs writes what the
+    last timed step computed (float32 / float64 .npy files, 64 MB at most), the same for two runs of one command line."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d = tmp_path / str(i)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--threads", "64", "--steps", "2", "--warmup", "1",
+               "--sampler-rng", "host", "--no-gemm-tuning", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"),
+                             timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["dtype"] == "f32"
+        assert not any(k.startswith("roofline") for k in line) and "cpu_baseline" not in line and "f32_mfma" not in line
+        files = {f.name[:-4]: np.load(f) for f in d.glob("*.npy")}
+        assert "returns" in files and any(k.startswith("actor.") for k in files) and any(k.startswith("critic.") for k in files)
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(f.stat().st_size for f in d.glob("*.npy")) <= 64 << 20
+        for k, v in line["train_info"].items():
+            assert float(files["train_info." + k]) == pytest.approx(v, rel=1e-5, abs=1e-6), k
+        runs.append(files)
+    assert sorted(runs[0]) == sorted(runs[1])
+    for k in runs[0]:           # host permutations, same seeds: the same update
+        np.testing.assert_allclose(runs[0][k], runs[1][k], rtol=1e-4, atol=1e-6, err_msg=k)
+
+
 def test_two_ranks_on_one_gpu_strong_scaling_path():
     """The driver's multi-GPU launch line with 2 ranks, both mapped onto the one GPU of this box (gloo
     carries the collectives because RCCL refuses duplicate devices): sharding of the rollout threads,
@@ -105,7 +136,7 @@ def test_two_ranks_on_one_gpu_strong_scaling_path():
     env.update(MAPPO_DIST_BACKEND="gloo", MAPPO_SINGLE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29611", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "1", "--threads", "64", "--sampler-rng", "host"]
+           "--gpus", "2", "--steps", "1", "--warmup", "1", "--threads", "64", "--sampler-rng", "host", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -126,7 +157,7 @@ def test_plain_gpus_flag_runs_two_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--threads", "64", "--steps", "1",
-                          "--warmup", "1", "--sampler-rng", "host", "--no-gemm-tuning"],
+                          "--warmup", "1", "--sampler-rng", "host", "--no-gemm-tuning", "--full"],
                          capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -152,7 +183,7 @@ def test_two_ranks_over_rccl_when_the_box_has_two_gpus():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MAPPO_DIST_BACKEND", "MAPPO_SINGLE_DEVICE"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--threads", "64", "--steps", "2",
-                          "--warmup", "1", "--no-gemm-tuning"], capture_output=True, text=True, env=env, timeout=900)
+                          "--warmup", "1", "--no-gemm-tuning", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines

@@ -7,7 +7,7 @@ OUT=$REPO/gpurun_out/bench_prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ulimit -c 0
-timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT -o $NAME -- python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/$NAME.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT -o $NAME -- python $REPO/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline "$@" > $OUT/$NAME.log 2>&1
 F=$(find $OUT -name "${NAME}_kernel_stats.csv" | head -1)
 python - "$F" <<'P'
 import csv, sys

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 ulimit -c 0
 
 # 1. per-kernel time of the whole hot path (1 warm-up + 1 timed step, no CPU baseline)
-rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_bench -o bench -- python $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $OUT/prof_bench.log 2>&1
+rocprofv3 --kernel-trace --stats -f csv -d $OUT/prof_bench -o bench -- python $REPO/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > $OUT/prof_bench.log 2>&1
 tail -2 $OUT/prof_bench.log
 
 # 2. counters of the GAE scan (separate passes: FETCH_SIZE and WRITE_SIZE do not fit together)

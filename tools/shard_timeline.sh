@@ -10,8 +10,8 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ulimit -c 0
 export MAPPO_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29581
-timeout 300 python $REPO/bench.py --threads $THREADS --steps 10 --warmup 2 --no-cpu-baseline 2>&1 | tail -1 > $OUT/bench.json
-timeout 300 rocprofv3 --kernel-trace -f csv -d $OUT/trace -o t -- python $REPO/bench.py --threads $THREADS --steps 4 --warmup 1 --no-cpu-baseline > $OUT/trace.log 2>&1
+timeout 300 python $REPO/bench.py --threads $THREADS --steps 10 --warmup 2 --full --no-cpu-baseline 2>&1 | tail -1 > $OUT/bench.json
+timeout 300 rocprofv3 --kernel-trace -f csv -d $OUT/trace -o t -- python $REPO/bench.py --threads $THREADS --steps 4 --warmup 1 --full --no-cpu-baseline > $OUT/trace.log 2>&1
 find $OUT -name "*.db" -delete
 cd $REPO
 python tools/shard_timeline.py $OUT > $OUT/summary.json 2> $OUT/summary.err
