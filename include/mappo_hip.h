@@ -394,6 +394,18 @@ int mappo_ppo_loss_f32(const mappo_ppo_loss_t* args, mappo_stream_t stream);
 int mappo_categorical_sample(const float* logits, const float* available, const float* noise, int64_t* actions,
                              float* log_probs, int64_t rows, int n_actions, mappo_stream_t stream);
 
+/* ------------------------------------------------------ K14 for MultiDiscrete heads: one launch for all sub-heads ----
+ * ACTLayer.forward's multi-discrete branch (onpolicy/algorithms/utils/act.py) samples every sub-head as above (no
+ * availability mask) and concatenates actions and log-probs.  logits [rows, sum_k head_sizes[k]] (the sub-heads'
+ * logits side by side); noise: host array of num_heads device pointers, noise[k] [rows, head_sizes[k]] (> 0) -- the
+ * Exponential(1) draws of sub-head k's torch.multinomial, drawn in head order; head_sizes: host array.  Outputs
+ * actions [rows, num_heads] int64 and log_probs [rows, num_heads] (per sub-head, not summed).
+ * num_heads <= MAPPO_MULTI_SAMPLE_MAX_HEADS, sum of head_sizes <= 64. */
+#define MAPPO_MULTI_SAMPLE_MAX_HEADS 8
+int mappo_multi_categorical_sample(const float* logits, const float* const* noise, const int* head_sizes,
+                                   int num_heads, int64_t* actions, float* log_probs, int64_t rows,
+                                   mappo_stream_t stream);
+
 /* --------------------------------------------------------------- K8: GRU cell gates ----
  * Everything of one GRU step that is not a GEMM (reference onpolicy/algorithms/utils/rnn.py:7-80 runs
  * nn.GRU; PyTorch cell, gates stacked r|z|n), reading / writing the per-sequence buffers in place:
@@ -718,6 +730,23 @@ int mappo_simple_spread_step(double* pos, double* vel, double* landmarks, int64_
                              const double* fresh_pos, const double* fresh_landmarks, float* obs, float* rewards,
                              uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents, int num_landmarks,
                              int world_length, int auto_reset, mappo_stream_t stream);
+
+/* ----------------------------------------------------- K11 family: simple_reference worlds on the device ----
+ * One env step of `n_worlds` referential-communication worlds (reference onpolicy/envs/mpe/scenarios/simple_reference.py,
+ * environment.py:115-255, core.py:207-288; 2 agents, 3 landmarks, no contacts) as one launch.  State is updated in
+ * place: pos / vel [n, 2, 2] and landmarks [n, 3, 2] float64, t [n] int64, goals [n, 2] int64 (each agent's goal
+ * landmark, 0..2), comm [n, 2] int64 (each agent's last communication symbol, -1 = silent).  actions [n, 2, 2] int64
+ * (movement 0..4, symbol 0..9).  Worlds whose t reaches world_length report done and (auto_reset) restart from
+ * fresh_pos [n, 2, 2], 0.8 * fresh_landmarks [n, 3, 2] (uniform(-1, 1) draws) and fresh_goals [n, 2], with zero
+ * velocity and silent agents.  Outputs: obs [n, 2, 21] float32 (velocity, landmarks relative to the agent, the
+ * colour of the agent's goal landmark, the other agent's symbol one-hot; of the restarted world where one restarted),
+ * rewards [n, 2, 1] float32 (shared: r_0 + r_1), dones [n, 2] bytes, per_agent [n, 2] float64 (r_i, the
+ * individual_reward info). */
+int mappo_simple_reference_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goals, int64_t* comm,
+                                const int64_t* actions, const double* fresh_pos, const double* fresh_landmarks,
+                                const int64_t* fresh_goals, float* obs, float* rewards, uint8_t* dones,
+                                double* per_agent, int64_t n_worlds, int world_length, int auto_reset,
+                                mappo_stream_t stream);
 
 /* --------------------------------------------------------------------- misc ---- */
 int         mappo_abi_version(void);

@@ -159,6 +159,7 @@ SIGNATURES = {
     "mappo_clip_adam": (_int, [ctypes.POINTER(Adam), _vp]),
     "mappo_ppo_loss_f32": (_int, [ctypes.POINTER(PPOLoss), _vp]),
     "mappo_categorical_sample": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
+    "mappo_multi_categorical_sample": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _i64, _vp]),
     "mappo_minibatch_workspace_ints": (_i64, [_i64, _int]),
     "mappo_minibatch_indices": (_int, [_i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "mappo_mlp_forward": (_int, [ctypes.POINTER(MLP), _vp]),
@@ -180,6 +181,7 @@ SIGNATURES = {
     "mappo_linear512_wgrad_workspace_floats": (_i64, [_int]),
     "mappo_linear512_wgrad": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "mappo_simple_spread_step": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
+    "mappo_simple_reference_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
     "mappo_abi_version": (_int, []),
     "mappo_build_info": (ctypes.c_char_p, []),
     "mappo_error_string": (ctypes.c_char_p, [_int]),
@@ -199,7 +201,8 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise NativeError(
                 "libmappo_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C on-policy_amd/csrc`. There is no CPU fallback." % LIB_PATH)
+                "g.build()'` or `make -C on-policy_amd/csrc -f Makefile -f ../csrc_ext/ext.mk`. There is no CPU "
+                "fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)  # AttributeError here = header / library mismatch

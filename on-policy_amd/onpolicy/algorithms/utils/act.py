@@ -35,6 +35,7 @@ class ACTLayer(nn.Module):
             dims = action_space.high - action_space.low + 1
             self.action_outs = nn.ModuleList(
                 [Categorical(inputs_dim, int(d), use_orthogonal, gain) for d in dims])
+            self.head_sizes = [int(d) for d in dims]
         else:  # [Box, Discrete]
             self.mixed_action = True
             self.action_outs = nn.ModuleList([
@@ -47,6 +48,13 @@ class ACTLayer(nn.Module):
         return self.action_out(x, available_actions)
 
     def forward(self, x, available_actions=None, deterministic=False):
+        if self.multi_discrete and not deterministic:
+            from . import fused_loss
+            if fused_loss.multi_sample_supported(x, self.head_sizes):
+                # K14 for all sub-heads in one launch; the sub-heads' Linears stay separate modules (checkpoint keys
+                # action_outs.{k}.linear.*), their logits side by side
+                logits = torch.cat([head.linear(x) for head in self.action_outs], -1)
+                return fused_loss.sample_multi_categorical(logits, self.head_sizes)
         if self.mixed_action or self.multi_discrete:
             actions, log_probs = [], []
             for head in self.action_outs:

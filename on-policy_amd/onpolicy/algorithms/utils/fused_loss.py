@@ -75,3 +75,36 @@ def sample_categorical(logits, available_actions=None):
     _native.check(_native.lib().mappo_categorical_sample(p(lg), p(avail), p(noise), p(actions), p(logp), rows, na,
                                                          _native.stream_of(lg.device)), "mappo_categorical_sample")
     return actions, logp
+
+
+MULTI_SAMPLE_MAX_HEADS = 8
+
+
+def multi_sample_supported(x, head_sizes):
+    """The MultiDiscrete form of K14 takes this head's rollout sampling: float32 HIP features, at most 8 sub-heads of
+    <= 64 actions in all, device-sampling mode, no autograd (``MAPPO_FUSED_SAMPLE=0`` disables it, as for K14)."""
+    from . import distributions
+    return (os.environ.get("MAPPO_FUSED_SAMPLE", "1") != "0" and torch.is_tensor(x) and x.is_cuda
+            and x.dtype == torch.float32 and x.dim() == 2 and 0 < len(head_sizes) <= MULTI_SAMPLE_MAX_HEADS
+            and sum(head_sizes) <= 64 and not torch.is_grad_enabled() and distributions.SAMPLING_RNG == "device")
+
+
+def sample_multi_categorical(logits, head_sizes):
+    """(actions [rows, k] int64, log-probs [rows, k]) of one draw per row and sub-head from the sub-heads' logits laid side
+    by side in ``logits`` [rows, sum head_sizes] (``mappo_multi_categorical_sample``): what ACTLayer.forward's
+    multi-discrete branch gives with one FixedCategorical per sub-head.  The Exponential(1) noise is drawn per sub-head in
+    head order, as the framework's per-head torch.multinomial(p, 1) draws it, so both paths consume the same stream."""
+    import ctypes
+    rows = logits.shape[0]
+    k = len(head_sizes)
+    lg = logits.detach().contiguous()
+    noise = [torch.empty((rows, int(n)), dtype=torch.float32, device=lg.device).exponential_(1.0) for n in head_sizes]
+    actions = torch.empty((rows, k), dtype=torch.int64, device=lg.device)
+    logp = torch.empty((rows, k), dtype=torch.float32, device=lg.device)
+    p = _native.ptr
+    noise_ptrs = (ctypes.c_void_p * k)(*[p(q) for q in noise])
+    sizes = (ctypes.c_int * k)(*[int(n) for n in head_sizes])
+    _native.check(_native.lib().mappo_multi_categorical_sample(p(lg), noise_ptrs, sizes, k, p(actions), p(logp), rows,
+                                                               _native.stream_of(lg.device)),
+                  "mappo_multi_categorical_sample")
+    return actions, logp

@@ -26,6 +26,10 @@ import torch
 from onpolicy.utils.graph_capture import capturing
 
 
+# the state tensors of an env that does not declare its own (``state_names``): simple_spread's worlds
+DEFAULT_STATE_NAMES = ("pos", "vel", "landmarks", "t")
+
+
 class RolloutGraph(object):
     WARMUP = 3
 
@@ -92,9 +96,14 @@ class RolloutGraph(object):
         share_next = r._share(obs, N).contiguous() if r.use_centralized_V else obs
         return (share_next, obs, rnn_a, rnn_c, actions, logp, values, rewards, masks), infos
 
+    def _state_names(self):
+        """The env's state tensors that a replay advances in place: what the env declares (``state_names``), else those of
+        simple_spread's worlds."""
+        return tuple(getattr(self.r.envs, "state_names", DEFAULT_STATE_NAMES))
+
     def _env_state(self):
         e = self.r.envs
-        return {k: getattr(e, k).clone() for k in ("pos", "vel", "landmarks", "t")}, e.rng.get_state(), \
+        return {k: getattr(e, k).clone() for k in self._state_names()}, e.rng.get_state(), \
             torch.cuda.get_rng_state(self.r.buffer.device)
 
     class _StaticHead(object):
@@ -134,7 +143,7 @@ class RolloutGraph(object):
         keep = (self.cur_obs.clone(), self.cur_masks.clone(),
                 self.cur_rnn_a.clone() if self.recurrent else None, self.cur_rnn_c.clone() if self.recurrent else None)
         snap = self._env_state()
-        state_ptrs = {k: getattr(r.envs, k).data_ptr() for k in ("pos", "vel", "landmarks", "t")}
+        state_ptrs = {k: getattr(r.envs, k).data_ptr() for k in self._state_names()}
         torch.cuda.synchronize(dev)
         try:        # (warm-up included: whatever fails in here, worlds / generators / carried state go back where they were)
             with self._StaticHead(self):

@@ -4,17 +4,28 @@ onpolicy/scripts/train/train_mpe.py (main :64, parse_args :52-61, env factories 
 same algorithm-name -> recurrent-flag rewrite, same config dict handed to ``MPERunner``.
 
 Differences: simple_spread comes from the in-tree vectorised implementation (no gym / subprocess workers;
-``--use_device_env`` keeps the training worlds on the GPU next to policy and buffer);
-other scenarios are built per worker from an external env tree (MAPPO_ENVS_PATH); wandb / setproctitle are optional.
+``--use_device_env`` keeps the training worlds on the GPU next to policy and buffer); with ``--use_device_env``
+simple_reference comes from the in-tree device implementation as well (envs/mpe/simple_reference.py, shared-policy
+runner only); every other case -- simple_reference without the flag, any other scenario, and the eval envs of
+``--use_eval`` in every case -- is built per worker from an external env tree (MAPPO_ENVS_PATH);
+wandb / setproctitle are optional.
 Example (BASELINE.json configs[0]):
     python -m onpolicy.scripts.train.train_mpe --env_name MPE --scenario_name simple_spread \\
         --num_agents 3 --num_landmarks 3 --n_rollout_threads 8 --episode_length 25 \\
         --num_env_steps 20000 --ppo_epoch 10 --use_ReLU --use_wandb
+The reference's train_mpe_reference.sh on the device:
+    python -m onpolicy.scripts.train.train_mpe --env_name MPE --algorithm_name rmappo --scenario_name simple_reference \
+        --num_agents 2 --num_landmarks 3 --n_rollout_threads 128 --num_mini_batch 1 --episode_length 25 \
+        --num_env_steps 3000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 --critic_lr 7e-4 --use_device_env
 """
 import sys
 
 from onpolicy.config import get_config
 from onpolicy.scripts.train import _launch
+
+
+# scenarios with an in-tree device implementation (--use_device_env)
+DEVICE_SCENARIOS = ("simple_spread", "simple_reference")
 
 
 def make_train_env(all_args, n_threads=None, seed_offset=0, device=None):
@@ -24,6 +35,10 @@ def make_train_env(all_args, n_threads=None, seed_offset=0, device=None):
         from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread
         return TorchSimpleSpread(n, all_args.num_agents, all_args.num_landmarks, all_args.episode_length,
                                  seed=all_args.seed + seed_offset, device=device)
+    if all_args.scenario_name == "simple_reference" and device is not None:     # worlds held on the device
+        from onpolicy.envs.mpe.simple_reference import TorchSimpleReference
+        return TorchSimpleReference(n, all_args.num_agents, all_args.num_landmarks, all_args.episode_length,
+                                    seed=all_args.seed + seed_offset, device=device)
     if all_args.scenario_name == "simple_spread":       # built in, all worlds advanced by one numpy pass
         from onpolicy.envs.mpe.simple_spread import VecSimpleSpread
         return VecSimpleSpread(n, all_args.num_agents, all_args.num_landmarks, all_args.episode_length,
@@ -47,8 +62,8 @@ def parse_args(args, parser):
     parser.add_argument("--num_landmarks", type=int, default=3)
     parser.add_argument('--num_agents', type=int, default=2, help="number of players")
     parser.add_argument('--use_device_env', action='store_true', default=False,
-                        help="simple_spread with the training worlds held as tensors on the policy's device "
-                             "(shared-policy runner): no per-step host round trip")
+                        help="simple_spread or simple_reference with the training worlds held as tensors on the "
+                             "policy's device (shared-policy runner): no per-step host round trip")
     return parser.parse_known_args(args)[0]
 
 
@@ -61,7 +76,7 @@ def main(args):
     run_dir = _launch.new_run_dir(all_args, all_args.scenario_name)
     _launch.seed_everything(all_args)
     shared = all_args.share_policy and all_args.algorithm_name not in ("happo", "hatrpo")
-    if all_args.use_device_env and not (shared and all_args.scenario_name == "simple_spread"):
+    if all_args.use_device_env and not (shared and all_args.scenario_name in DEVICE_SCENARIOS):
         raise NotImplementedError("--use_device_env: simple_spread with the shared-policy runner only")
     envs = make_train_env(all_args, device=device if all_args.use_device_env else None)
     eval_envs = make_train_env(all_args, all_args.n_eval_rollout_threads, 50000) if all_args.use_eval else None
