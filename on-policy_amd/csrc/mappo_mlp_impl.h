@@ -1157,6 +1157,52 @@ __device__ __forceinline__ void split3(const float* x, bf8& p1, bf8& p2, bf8& p3
     }
 }
 
+// Instruction placement beside the matrix pipe (device only; the host build of the emulator sees nothing).  A
+// v_mfma_f32_32x32x16_bf16 holds the pipe for 32 cycles and hides up to 24 cycles of the same wave's other issue (five
+// single-issue vector instructions); what the compiler leaves in ONE gap after a burst of MFMAs runs for its full length.
+// MAPPO_MFMA_GAP(DS, VALU): "one MFMA, then DS LDS reads and VALU vector instructions" of the region that ends at the
+// next sched_fence (LLVM's sched_group_barrier pipeline: masks MFMA 0x8, DS read 0x100, VALU 0x2).
+// MAPPO_SINGLE_ISSUE(v): v stays a scalar float for the vectoriser, so that its arithmetic is not merged with its
+// neighbour's into packed-f32 instructions (v_pk_add_f32 next to MFMAs costs more than the two v_sub_f32 it replaces).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MAPPO_MFMA_GAP(DS, VALU)                                    \
+    do {                                                            \
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          \
+        __builtin_amdgcn_sched_group_barrier(0x100, DS, 0);         \
+        __builtin_amdgcn_sched_group_barrier(0x002, VALU, 0);       \
+    } while (0)
+#define MAPPO_SINGLE_ISSUE(v) asm("" : "+v"(v))
+#else
+#define MAPPO_MFMA_GAP(DS, VALU) do { } while (0)
+#define MAPPO_SINGLE_ISSUE(v) do { } while (0)
+#endif
+
+// split3's arithmetic, value for value, as single-issue instructions: for the splits that run in the shadow of MFMAs.
+// Two values at a time: one v_cvt_pk_bf16_f32 per plane and pair, whose halves are widened again by a shift and a mask
+// (the pair is pinned as ONE register so that the compiler does not convert each value a second time on its own).
+typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split3_single(const float* x, bf8& p1, bf8& p2, bf8& p3) {
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        bf2 q1 = {(__bf16)x[e], (__bf16)x[e + 1]};
+        MAPPO_SINGLE_ISSUE(q1);
+        float r0 = x[e] - (float)q1[0], r1 = x[e + 1] - (float)q1[1];
+        MAPPO_SINGLE_ISSUE(r0);
+        MAPPO_SINGLE_ISSUE(r1);
+        bf2 q2 = {(__bf16)r0, (__bf16)r1};
+        MAPPO_SINGLE_ISSUE(q2);
+        float t0 = r0 - (float)q2[0], t1 = r1 - (float)q2[1];
+        MAPPO_SINGLE_ISSUE(t0);
+        MAPPO_SINGLE_ISSUE(t1);
+        p1[e] = q1[0];
+        p1[e + 1] = q1[1];
+        p2[e] = q2[0];
+        p2[e + 1] = q2[1];
+        p3[e] = (__bf16)t0;
+        p3[e + 1] = (__bf16)t1;
+    }
+}
+
 struct XBuf8 {
     v4 x[8];
 };
@@ -1286,14 +1332,21 @@ __global__ void __launch_bounds__(64 * 4, 1) mlp_fwd4_kernel(FwdArgs a) {
         }
     };
     f32x16 acc[2];
-    auto mfma_steps = [&](const XBuf8& B, int kc, auto nsteps) {
-        constexpr int NS = decltype(nsteps)::value;
-        const float* wt = lds + o.w1 + kc * 6144 + lane * 4;
-        bf8 an[3][2];
+    // The operand pipeline, one k = 16 step ahead: while the 12 MFMAs of a step run, the NEXT step's eight floats are split
+    // (~45 single-issue vector instructions) and its six A planes are read from LDS -- four vector instructions and at
+    // most one LDS read per MFMA gap, placed by MAPPO_MFMA_GAP.  The step after a chunk's last one is step 0 of the next
+    // chunk (buffer Bn, weight chunk kcn), after a tile's last one step 0 of the wave's next tile: an / bn live across
+    // chunks and tiles.  The order of the six terms and of the steps on each accumulator is the unpipelined loop's.
+    bf8 an[3][2], bn[3];
+    auto a_planes = [&](int kc, int s) {
+        const float* wt = lds + o.w1 + kc * 6144 + s * 512 + lane * 4;
 #pragma unroll
         for (int p = 0; p < 3; ++p)
 #pragma unroll
             for (int t = 0; t < 2; ++t) an[p][t] = *reinterpret_cast<const bf8*>(wt + p * 2048 + t * 256);
+    };
+    auto mfma_steps = [&](const XBuf8& B, const XBuf8& Bn, int kc, int kcn, auto nsteps) {
+        constexpr int NS = decltype(nsteps)::value;
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             bf8 af[3][2];
@@ -1301,22 +1354,25 @@ __global__ void __launch_bounds__(64 * 4, 1) mlp_fwd4_kernel(FwdArgs a) {
             for (int p = 0; p < 3; ++p)
 #pragma unroll
                 for (int t = 0; t < 2; ++t) af[p][t] = an[p][t];
-            if (s + 1 < NS) {
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-                        an[p][t] = *reinterpret_cast<const bf8*>(wt + p * 2048 + ((s + 1 < NS ? s + 1 : 0) * 2 + t) * 256);
-            }
+            const bf8 b1 = bn[0], b2 = bn[1], b3 = bn[2];
             prim::sched_fence();
             float r[8];
+            if (s + 1 < NS) {
+                a_planes(kc, s + 1 < NS ? s + 1 : 0);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                r[i] = B.x[2 * s][i];
-                r[4 + i] = B.x[2 * s + 1][i];
+                for (int i = 0; i < 4; ++i) {
+                    r[i] = B.x[s + 1 < NS ? 2 * s + 2 : 0][i];
+                    r[4 + i] = B.x[s + 1 < NS ? 2 * s + 3 : 1][i];
+                }
+            } else {
+                a_planes(kcn, 0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    r[i] = Bn.x[0][i];
+                    r[4 + i] = Bn.x[1][i];
+                }
             }
-            bf8 b1, b2, b3;
-            split3(r, b1, b2, b3);
+            split3_single(r, bn[0], bn[1], bn[2]);
             // smallest terms first
             acc[0] = prim::mfma_bf16(af[0][0], b3, acc[0]);
             acc[1] = prim::mfma_bf16(af[0][1], b3, acc[1]);
@@ -1330,20 +1386,34 @@ __global__ void __launch_bounds__(64 * 4, 1) mlp_fwd4_kernel(FwdArgs a) {
             acc[1] = prim::mfma_bf16(af[1][1], b1, acc[1]);
             acc[0] = prim::mfma_bf16(af[0][0], b1, acc[0]);
             acc[1] = prim::mfma_bf16(af[0][1], b1, acc[1]);
+            MAPPO_MFMA_GAP(1, 4); MAPPO_MFMA_GAP(1, 4); MAPPO_MFMA_GAP(1, 4); MAPPO_MFMA_GAP(1, 4);
+            MAPPO_MFMA_GAP(1, 4); MAPPO_MFMA_GAP(1, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4);
+            MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4);
         }
     };
-    auto mfma_chunk = [&](const XBuf8& B, int kc) { mfma_steps(B, kc, mlp_int<4>{}); };
-    auto mfma_last = [&](const XBuf8& B, int kc) { mfma_steps(B, kc, mlp_int<NSL>{}); };
+    auto mfma_chunk = [&](const XBuf8& B, const XBuf8& Bn, int kc, int kcn) { mfma_steps(B, Bn, kc, kcn, mlp_int<4>{}); };
+    auto mfma_last = [&](const XBuf8& B, const XBuf8& Bn, int kc, int kcn) { mfma_steps(B, Bn, kc, kcn, mlp_int<NSL>{}); };
 
     XBuf8 B0, B1, B2;
     issue(B0);
     issue(B1);
     issue(B2);
+    {
+        float r[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            r[i] = B0.x[0][i];
+            r[4 + i] = B0.x[1][i];
+        }
+        split3_single(r, bn[0], bn[1], bn[2]);
+    }
     const bool cstamp = a.dbg != nullptr && blockIdx.x == 0 && wave == 0 && lane == 0;
-#define MAPPO_F4_STEP(B, KC) do { mfma_chunk(B, KC); issue(B); } while (0)
-#define MAPPO_F4_LAST(B, KC) do { mfma_last(B, KC); issue(B); } while (0)
+    // (BN: the ring's next buffer, which holds chunk KC + 1 of this tile or chunk 0 of the next one)
+#define MAPPO_F4_STEP(B, BN, KC) do { mfma_chunk(B, BN, KC, (KC) + 1 < nsc ? (KC) + 1 : 0); issue(B); } while (0)
+#define MAPPO_F4_LAST(B, BN, KC) do { mfma_last(B, BN, KC, 0); issue(B); } while (0)
     for (long long m = 0; m < my_tiles;) {
         if (cstamp && m < 15) a.dbg[4 * m] = prim::clock();
+        a_planes(0, 0);             // (read again rather than kept through the tails: 24 registers the tails need)
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -1352,19 +1422,19 @@ __global__ void __launch_bounds__(64 * 4, 1) mlp_fwd4_kernel(FwdArgs a) {
         // (the ring of chunk buffers with static names, like version 3)
         if (NSL == 4) {
             for (; kc + 3 <= nsc; kc += 3) {
-                MAPPO_F4_STEP(B0, kc);
-                MAPPO_F4_STEP(B1, kc + 1);
-                MAPPO_F4_STEP(B2, kc + 2);
+                MAPPO_F4_STEP(B0, B1, kc);
+                MAPPO_F4_STEP(B1, B2, kc + 1);
+                MAPPO_F4_STEP(B2, B0, kc + 2);
             }
             if (nsc - kc == 1) {
-                MAPPO_F4_STEP(B0, kc);
+                MAPPO_F4_STEP(B0, B1, kc);
                 const XBuf8 t = B0;
                 B0 = B1;
                 B1 = B2;
                 B2 = t;
             } else if (nsc - kc == 2) {
-                MAPPO_F4_STEP(B0, kc);
-                MAPPO_F4_STEP(B1, kc + 1);
+                MAPPO_F4_STEP(B0, B1, kc);
+                MAPPO_F4_STEP(B1, B2, kc + 1);
                 const XBuf8 t = B2;
                 B2 = B1;
                 B1 = B0;
@@ -1372,27 +1442,27 @@ __global__ void __launch_bounds__(64 * 4, 1) mlp_fwd4_kernel(FwdArgs a) {
             }
         } else {
             for (; kc + 3 < nsc; kc += 3) {
-                MAPPO_F4_STEP(B0, kc);
-                MAPPO_F4_STEP(B1, kc + 1);
-                MAPPO_F4_STEP(B2, kc + 2);
+                MAPPO_F4_STEP(B0, B1, kc);
+                MAPPO_F4_STEP(B1, B2, kc + 1);
+                MAPPO_F4_STEP(B2, B0, kc + 2);
             }
             if (nsc - kc == 1) {
-                MAPPO_F4_LAST(B0, kc);
+                MAPPO_F4_LAST(B0, B1, kc);
                 const XBuf8 t = B0;
                 B0 = B1;
                 B1 = B2;
                 B2 = t;
             } else if (nsc - kc == 2) {
-                MAPPO_F4_STEP(B0, kc);
-                MAPPO_F4_LAST(B1, kc + 1);
+                MAPPO_F4_STEP(B0, B1, kc);
+                MAPPO_F4_LAST(B1, B2, kc + 1);
                 const XBuf8 t = B2;
                 B2 = B1;
                 B1 = B0;
                 B0 = t;
             } else {
-                MAPPO_F4_STEP(B0, kc);
-                MAPPO_F4_STEP(B1, kc + 1);
-                MAPPO_F4_LAST(B2, kc + 2);
+                MAPPO_F4_STEP(B0, B1, kc);
+                MAPPO_F4_STEP(B1, B2, kc + 1);
+                MAPPO_F4_LAST(B2, B0, kc + 2);
             }
         }
         if (cstamp && m < 15) a.dbg[4 * m + 1] = prim::clock();
@@ -2658,13 +2728,16 @@ __device__ __forceinline__ void dw1_tile_steps6(const float* xt, const float* dz
     for (int i = 0; i < NT; ++i)
 #pragma unroll
         for (int e = 0; e < 8; ++e) b[i][e] = xt[i * (kD2Rows * 32) + (8 * h + e) * 32 + c];
-    bf8 A[2][3];
+    bf8 A[2][3], Bn[3];
     split3(a0, A[0][0], A[0][1], A[0][2]);
     split3(a1, A[1][0], A[1][1], A[1][2]);
+    split3(b[0], Bn[0], Bn[1], Bn[2]);
+    // (k tile i + 1's x is split while k tile i's 12 MFMAs run: four of its ~45 vector instructions per MFMA gap)
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
-        bf8 B[3];
-        split3(b[i], B[0], B[1], B[2]);
+        const bf8 B[3] = {Bn[0], Bn[1], Bn[2]};
+        prim::sched_fence();
+        if (i + 1 < NT) split3_single(b[i + 1 < NT ? i + 1 : 0], Bn[0], Bn[1], Bn[2]);
         acc[i][0] = prim::mfma_bf16(A[0][0], B[2], acc[i][0]);
         acc[i][1] = prim::mfma_bf16(A[1][0], B[2], acc[i][1]);
         acc[i][0] = prim::mfma_bf16(A[0][2], B[0], acc[i][0]);
@@ -2677,6 +2750,11 @@ __device__ __forceinline__ void dw1_tile_steps6(const float* xt, const float* dz
         acc[i][1] = prim::mfma_bf16(A[1][1], B[0], acc[i][1]);
         acc[i][0] = prim::mfma_bf16(A[0][0], B[0], acc[i][0]);
         acc[i][1] = prim::mfma_bf16(A[1][0], B[0], acc[i][1]);
+        if (i + 1 < NT) {
+            MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4);
+            MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4);
+            MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4);
+        }
     }
 }
 

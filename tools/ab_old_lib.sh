@@ -8,7 +8,10 @@ REV=${1:-HEAD}
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 WT=$(mktemp -d /tmp/mappo_old_XXXX)
 git -C "$ROOT" worktree add -q --detach "$WT" "$REV"
-make -s -C "$WT/on-policy_amd/csrc" >/dev/null
+# (the same make line as build(): csrc/ plus the entry points of csrc_ext/, where that commit has them)
+EXT=
+[ -f "$WT/on-policy_amd/csrc_ext/ext.mk" ] && EXT="-f ../csrc_ext/ext.mk"
+make -s -C "$WT/on-policy_amd/csrc" -f Makefile $EXT -j4 ARCH=gfx950 >/dev/null
 cp "$WT/on-policy_amd/lib/libmappo_hip.so" "$ROOT/on-policy_amd/lib/libmappo_hip_OLD.so"
 git -C "$ROOT" worktree remove --force "$WT"
 echo "$ROOT/on-policy_amd/lib/libmappo_hip_OLD.so  <-  $(git -C "$ROOT" rev-parse --short "$REV")"
