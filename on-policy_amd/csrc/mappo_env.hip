@@ -1,12 +1,18 @@
-// K11: one step of all simple_spread worlds as ONE launch (row f1 of the scope table: the device-resident rollout loop).
-// The worlds of config 1 / config 3 (MPE cooperative navigation; reference onpolicy/envs/mpe/core.py:120-190 physics,
-// environment.py:100-180 step / action decoding, scenarios/simple_spread.py:60-103 reward / observation) are a few
-// dozen float64 operations per agent pair.  Written as array operations on device tensors a step is ~60 small launches
-// (measured: 140 ms per step at 4096 worlds, ten times slower than the numpy env on the host); here a thread owns a
-// world and keeps its agents in registers.  State is float64 like the reference's numpy physics, observations and rewards
-// leave as float32.  Restarted worlds take their positions from `fresh_*`, uniform draws the caller makes every step
+// K11 family: one step of all worlds of a multi-agent particle scenario as ONE launch (row f1 of the scope table: the
+// device-resident rollout loop).  The worlds (reference onpolicy/envs/mpe/core.py:120-190 physics, environment.py:100-255
+// step / action decoding, scenarios/*.py reward / observation) are a few dozen float64 operations per agent pair.
+// Written as array operations on device tensors a step is ~60 small launches (measured for simple_spread: 140 ms per
+// step at 4096 worlds, ten times slower than the numpy env on the host); here a thread owns a world and keeps its
+// entities in registers.  State is float64 like the reference's numpy physics and is advanced in place, observations and
+// rewards leave as float32.  Restarted worlds take their state from `fresh_*`, draws the caller makes every step
 // (branch-free: drawn for all worlds, used where a world restarts), so the trajectories are those of the tensor
-// implementation for the same generator.
+// implementation (envs/mpe/*.py::_step_ops) for the same generator.
+//
+// The particle physics every scenario shares is written once (World and the helpers below); a scenario's kernel adds its
+// own forces, extra state, reward and observation.  A world's entities are plain arrays px / py / vx / vy [agents] and
+// lx / ly [landmarks] that the helpers take by reference (separate arrays: one aggregate of all six does not come apart
+// into registers at 16 entities); they are templated on the array bound so that a scenario with fixed counts keeps them
+// at compile time and one with runtime counts stays fully unrolled.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mappo_hip.h"
@@ -17,48 +23,138 @@ namespace {
 constexpr int kMax = MAPPO_ENV_MAX_ENTITIES;
 constexpr double kDt = 0.1, kDamping = 0.25, kSens = 5.0, kForce = 1e2, kMargin = 1e-3, kSize = 0.15;
 
-struct Args {
-    double* pos;            // [N, A, 2]
-    double* vel;            // [N, A, 2]
-    double* land;           // [N, L, 2]
-    long long* t;           // [N]
-    const long long* act;   // [N, A] action indices 0..4
+// what the step of any particle world takes (A agents, L landmarks)
+struct World {
+    double* pos;                // [N, A, 2]
+    double* vel;                // [N, A, 2]
+    double* land;               // [N, L, 2]
+    long long* t;               // [N]
     const double* fresh_pos;    // [N, A, 2] uniform(-1, 1)
-    const double* fresh_land;   // [N, L, 2]
-    float* obs;             // [N, A, Do], Do = 4 + 2 L + 4 (A - 1)
-    float* rew;             // [N, A, 1]
-    unsigned char* done;    // [N, A] (bool)
-    double* per_agent;      // [N, A]
+    const double* fresh_land;   // [N, L, 2] uniform(-1, 1)
+    float* obs;                 // [N, A, Do]
+    float* rew;                 // [N, A, 1]
+    unsigned char* done;        // [N, A] (bool)
+    double* per_agent;          // [N, A]
     long long n;
-    int A, L, world_length, auto_reset;
+    int world_length, auto_reset;
+};
+
+template <int M>
+__device__ __forceinline__ void load_xy(const double* src, long long w, int count, double (&x)[M], double (&y)[M]) {
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        if (i >= count) continue;
+        x[i] = src[(w * count + i) * 2];
+        y[i] = src[(w * count + i) * 2 + 1];
+    }
+}
+
+template <int M>
+__device__ __forceinline__ void store_xy(double* dst, long long w, int count, const double (&x)[M],
+                                         const double (&y)[M]) {
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        if (i >= count) continue;
+        dst[(w * count + i) * 2] = x[i];
+        dst[(w * count + i) * 2 + 1] = y[i];
+    }
+}
+
+template <int MA, int ML>
+__device__ __forceinline__ void load_world(const World& s, long long w, int A, int L, double (&px)[MA],
+                                           double (&py)[MA], double (&vx)[MA], double (&vy)[MA], double (&lx)[ML],
+                                           double (&ly)[ML]) {
+    load_xy(s.pos, w, A, px, py);
+    load_xy(s.vel, w, A, vx, vy);
+    load_xy(s.land, w, L, lx, ly);
+}
+
+// movement index -> force (environment.py: u[0] += a[1] - a[2], u[1] += a[3] - a[4], x sensitivity)
+__device__ __forceinline__ void action_force(long long mv, double& fx, double& fy) {
+    fx = (mv == 1 ? 1.0 : mv == 2 ? -1.0 : 0.0) * kSens;
+    fy = (mv == 3 ? 1.0 : mv == 4 ? -1.0 : 0.0) * kSens;
+}
+
+// core.py:160-175: damping, then force * dt, then the position; no mass / max speed in these scenarios
+template <int MA>
+__device__ __forceinline__ void integrate(int A, double (&px)[MA], double (&py)[MA], double (&vx)[MA], double (&vy)[MA],
+                                          const double (&fx)[MA], const double (&fy)[MA]) {
+#pragma unroll
+    for (int i = 0; i < MA; ++i) {
+        if (i >= A) continue;
+        vx[i] = vx[i] * (1 - kDamping) + fx[i] * kDt;
+        vy[i] = vy[i] * (1 - kDamping) + fy[i] * kDt;
+        px[i] = px[i] + vx[i] * kDt;
+        py[i] = py[i] + vy[i] * kDt;
+    }
+}
+
+// individual rewards, the shared reward and the done flag of a world whose clock now shows t; -> the world restarts
+template <int MA>
+__device__ __forceinline__ bool write_outcome(const World& s, long long w, int A, long long t, const double (&pa)[MA],
+                                              double total) {
+    const bool done = t >= s.world_length;
+#pragma unroll
+    for (int i = 0; i < MA; ++i) {
+        if (i >= A) continue;
+        s.per_agent[w * A + i] = pa[i];
+        s.rew[w * A + i] = (float)total;
+        s.done[w * A + i] = done ? 1 : 0;
+    }
+    return done && s.auto_reset;
+}
+
+// a restarting world: agents at fresh_pos and at rest, landmarks at land_scale * fresh_land
+template <int MA, int ML>
+__device__ __forceinline__ void restart_from_fresh(const World& s, long long w, int A, int L, double land_scale,
+                                                   double (&px)[MA], double (&py)[MA], double (&vx)[MA],
+                                                   double (&vy)[MA], double (&lx)[ML], double (&ly)[ML]) {
+    load_xy(s.fresh_pos, w, A, px, py);
+    load_xy(s.fresh_land, w, L, lx, ly);
+#pragma unroll
+    for (int i = 0; i < MA; ++i) {
+        if (i < A) vx[i] = vy[i] = 0.0;
+    }
+#pragma unroll
+    for (int l = 0; l < ML; ++l) {
+        if (l >= L) continue;
+        lx[l] = land_scale * lx[l];
+        ly[l] = land_scale * ly[l];
+    }
+}
+
+// landmarks move only when a world restarts
+template <int MA, int ML>
+__device__ __forceinline__ void store_world(const World& s, long long w, int A, int L, long long t, bool restart,
+                                            const double (&px)[MA], const double (&py)[MA],
+                                            const double (&vx)[MA], const double (&vy)[MA],
+                                            const double (&lx)[ML], const double (&ly)[ML]) {
+    s.t[w] = t;
+    store_xy(s.pos, w, A, px, py);
+    store_xy(s.vel, w, A, vx, vy);
+    if (restart) store_xy(s.land, w, L, lx, ly);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// simple_spread (cooperative navigation; scenarios/simple_spread.py:60-103): A agents, L landmarks, soft contacts
+struct Args {
+    World s;
+    const long long* act;   // [N, A] action indices 0..4
+    int A, L;               // Do = 4 + 2 L + 4 (A - 1)
 };
 
 __global__ void __launch_bounds__(64) spread_step_kernel(Args a) {
     const long long w = (long long)blockIdx.x * 64 + threadIdx.x;
-    if (w >= a.n) return;
+    const World& s = a.s;
+    if (w >= s.n) return;
     const int A = a.A, L = a.L;
     double px[kMax], py[kMax], vx[kMax], vy[kMax], lx[kMax], ly[kMax];
-#pragma unroll
-    for (int i = 0; i < kMax; ++i) {
-        if (i < A) {
-            px[i] = a.pos[(w * A + i) * 2];
-            py[i] = a.pos[(w * A + i) * 2 + 1];
-            vx[i] = a.vel[(w * A + i) * 2];
-            vy[i] = a.vel[(w * A + i) * 2 + 1];
-        }
-        if (i < L) {
-            lx[i] = a.land[(w * L + i) * 2];
-            ly[i] = a.land[(w * L + i) * 2 + 1];
-        }
-    }
-    // ---- forces: action (environment.py: u[0] += a[1] - a[2], u[1] += a[3] - a[4], x sensitivity) + soft contacts
+    load_world(s, w, A, L, px, py, vx, vy, lx, ly);
+    // ---- forces: action + soft contacts
     double fx[kMax], fy[kMax];
 #pragma unroll
     for (int i = 0; i < kMax; ++i) {
-        if (i >= A) continue;
-        const long long ac = a.act[w * A + i];
-        fx[i] = (ac == 1 ? 1.0 : ac == 2 ? -1.0 : 0.0) * kSens;
-        fy[i] = (ac == 3 ? 1.0 : ac == 4 ? -1.0 : 0.0) * kSens;
+        if (i < A) action_force(a.act[w * A + i], fx[i], fy[i]);
     }
 #pragma unroll
     for (int i = 0; i < kMax; ++i) {
@@ -80,16 +176,8 @@ __global__ void __launch_bounds__(64) spread_step_kernel(Args a) {
         fx[i] += sx;
         fy[i] += sy;
     }
-    // ---- integrate (core.py:160-175: damping, then force * dt; no mass / max speed in this scenario)
-#pragma unroll
-    for (int i = 0; i < kMax; ++i) {
-        if (i >= A) continue;
-        vx[i] = vx[i] * (1 - kDamping) + fx[i] * kDt;
-        vy[i] = vy[i] * (1 - kDamping) + fy[i] * kDt;
-        px[i] = px[i] + vx[i] * kDt;
-        py[i] = py[i] + vy[i] * kDt;
-    }
-    long long t = a.t[w] + 1;
+    integrate(A, px, py, vx, vy, fx, fy);
+    long long t = s.t[w] + 1;
     // ---- reward (simple_spread.py:60-84): -sum over landmarks of the closest agent's distance, -1 per contact
     double cover = 0.0;
 #pragma unroll
@@ -119,51 +207,19 @@ __global__ void __launch_bounds__(64) spread_step_kernel(Args a) {
         pa[i] = cover - hits;
         total += pa[i];
     }
-    const bool done = t >= a.world_length;
-#pragma unroll
-    for (int i = 0; i < kMax; ++i) {
-        if (i >= A) continue;
-        a.per_agent[w * A + i] = pa[i];
-        a.rew[w * A + i] = (float)total;
-        a.done[w * A + i] = done ? 1 : 0;
-    }
-    if (done && a.auto_reset) {
+    const bool restart = write_outcome(s, w, A, t, pa, total);
+    if (restart) {
         t = 0;
-#pragma unroll
-        for (int i = 0; i < kMax; ++i) {
-            if (i < A) {
-                px[i] = a.fresh_pos[(w * A + i) * 2];
-                py[i] = a.fresh_pos[(w * A + i) * 2 + 1];
-                vx[i] = 0.0;
-                vy[i] = 0.0;
-            }
-            if (i < L) {
-                lx[i] = a.fresh_land[(w * L + i) * 2];
-                ly[i] = a.fresh_land[(w * L + i) * 2 + 1];
-            }
-        }
+        restart_from_fresh(s, w, A, L, 1.0, px, py, vx, vy, lx, ly);
     }
-    a.t[w] = t;
-#pragma unroll
-    for (int i = 0; i < kMax; ++i) {
-        if (i < A) {
-            a.pos[(w * A + i) * 2] = px[i];
-            a.pos[(w * A + i) * 2 + 1] = py[i];
-            a.vel[(w * A + i) * 2] = vx[i];
-            a.vel[(w * A + i) * 2 + 1] = vy[i];
-        }
-        if (i < L && done && a.auto_reset) {
-            a.land[(w * L + i) * 2] = lx[i];
-            a.land[(w * L + i) * 2 + 1] = ly[i];
-        }
-    }
+    store_world(s, w, A, L, t, restart, px, py, vx, vy, lx, ly);
     // ---- observation of the (possibly restarted) world: vel, pos, landmarks and other agents relative to the agent,
     // (A - 1) * 2 zero communication channels (simple_spread.py:86-103)
     const int Do = 4 + 2 * L + 4 * (A - 1);
 #pragma unroll
     for (int i = 0; i < kMax; ++i) {
         if (i >= A) continue;
-        float* o = a.obs + (w * A + i) * Do;
+        float* o = s.obs + (w * A + i) * Do;
         int k = 0;
         o[k++] = (float)vx[i];
         o[k++] = (float)vy[i];
@@ -185,6 +241,97 @@ __global__ void __launch_bounds__(64) spread_step_kernel(Args a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// simple_reference (referential communication; scenarios/simple_reference.py, core.py:207-288 communication state):
+// two agents, three landmarks, no contacts.  Each agent carries the goal landmark the OTHER agent has to reach and the
+// index of its last communication symbol (-1: silent), both advanced in place like the physics.
+constexpr int kRefAgents = 2, kRefLandmarks = 3, kRefSymbols = 10;
+constexpr int kRefObs = 2 + 2 * kRefLandmarks + 3 + kRefSymbols;     // 21
+constexpr double kRefLandmarkScale = 0.8;
+
+struct RefArgs {
+    World s;
+    long long* goal;                // [N, 2] goal landmark of each agent, 0..2
+    long long* comm;                // [N, 2] last symbol of each agent, -1 = silent
+    const long long* act;           // [N, 2, 2] (movement 0..4, symbol 0..9)
+    const long long* fresh_goal;    // [N, 2] 0..2
+};
+
+__global__ void __launch_bounds__(64) reference_step_kernel(RefArgs a) {
+    const long long w = (long long)blockIdx.x * 64 + threadIdx.x;
+    const World& s = a.s;
+    if (w >= s.n) return;
+    constexpr int A = kRefAgents, L = kRefLandmarks;
+    double px[A], py[A], vx[A], vy[A], lx[L], ly[L];
+    load_world(s, w, A, L, px, py, vx, vy, lx, ly);
+    long long goal[A], comm[A];
+    // ---- action force and integration; the symbol becomes the communication state
+    double fx[A], fy[A];
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+        goal[i] = a.goal[w * A + i];
+        action_force(a.act[(w * A + i) * 2], fx[i], fy[i]);
+        comm[i] = a.act[(w * A + i) * 2 + 1];
+    }
+    integrate(A, px, py, vx, vy, fx, fy);
+    long long t = s.t[w] + 1;
+    // ---- reward (simple_reference.py: -|goal_a - goal_b|^2, goal_a = the other agent), shared as r_0 + r_1
+    double pa[A];
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+        const int o = A - 1 - i;
+        const long long g = goal[i];
+        const double gx = g == 0 ? lx[0] : g == 1 ? lx[1] : lx[2];
+        const double gy = g == 0 ? ly[0] : g == 1 ? ly[1] : ly[2];
+        const double dx = px[o] - gx, dy = py[o] - gy;
+        pa[i] = -(dx * dx + dy * dy);
+    }
+    const bool restart = write_outcome(s, w, A, t, pa, pa[0] + pa[1]);
+    if (restart) {
+        t = 0;
+        restart_from_fresh(s, w, A, L, kRefLandmarkScale, px, py, vx, vy, lx, ly);
+    }
+    store_world(s, w, A, L, t, restart, px, py, vx, vy, lx, ly);
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+        if (restart) {
+            goal[i] = a.fresh_goal[w * A + i];
+            comm[i] = -1;
+            a.goal[w * A + i] = goal[i];
+        }
+        a.comm[w * A + i] = comm[i];
+    }
+    // ---- observation of the (possibly restarted) world (simple_reference.py observation): own velocity, landmarks
+    // relative to the agent, the colour of the agent's goal landmark, the other agent's communication state (one-hot)
+#pragma unroll
+    for (int i = 0; i < A; ++i) {
+        float* o = s.obs + (w * A + i) * kRefObs;
+        int k = 0;
+        o[k++] = (float)vx[i];
+        o[k++] = (float)vy[i];
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            o[k++] = (float)(lx[l] - px[i]);
+            o[k++] = (float)(ly[l] - py[i]);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[k++] = goal[i] == c ? 0.75f : 0.25f;     // palette: 0.75 on the landmark's own channel
+        const long long heard = comm[A - 1 - i];
+#pragma unroll
+        for (int sym = 0; sym < kRefSymbols; ++sym) o[k++] = heard == sym ? 1.f : 0.f;
+    }
+}
+
+// one thread per world, 64 to a block
+template <typename ArgsT>
+int launch_step(void (*kernel)(ArgsT), const ArgsT& a, mappo_stream_t stream_) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.s.n + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream_), a);
+    return (int)hipGetLastError();
+}
+
+long long* i64(int64_t* p) { return reinterpret_cast<long long*>(p); }
+const long long* i64(const int64_t* p) { return reinterpret_cast<const long long*>(p); }
+
 }  // namespace
 
 extern "C" int mappo_simple_spread_step(double* pos, double* vel, double* landmarks, int64_t* t, const int64_t* actions,
@@ -196,24 +343,22 @@ extern "C" int mappo_simple_spread_step(double* pos, double* vel, double* landma
     if (auto_reset && (!fresh_pos || !fresh_landmarks)) return MAPPO_E_NULL;
     if (n_worlds <= 0 || num_agents < 1 || num_landmarks < 1 || world_length < 1) return MAPPO_E_SHAPE;
     if (num_agents > kMax || num_landmarks > kMax) return MAPPO_E_TOO_MANY;
-    Args a;
-    a.pos = pos;
-    a.vel = vel;
-    a.land = landmarks;
-    a.t = reinterpret_cast<long long*>(t);
-    a.act = reinterpret_cast<const long long*>(actions);
-    a.fresh_pos = fresh_pos;
-    a.fresh_land = fresh_landmarks;
-    a.obs = obs;
-    a.rew = rewards;
-    a.done = dones;
-    a.per_agent = per_agent;
-    a.n = n_worlds;
-    a.A = num_agents;
-    a.L = num_landmarks;
-    a.world_length = world_length;
-    a.auto_reset = auto_reset;
-    hipLaunchKernelGGL(spread_step_kernel, dim3((unsigned)((n_worlds + 63) / 64)), dim3(64), 0,
-                       static_cast<hipStream_t>(stream_), a);
-    return (int)hipGetLastError();
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    return launch_step(spread_step_kernel, Args{s, i64(actions), num_agents, num_landmarks}, stream_);
+}
+
+extern "C" int mappo_simple_reference_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goals,
+                                           int64_t* comm, const int64_t* actions, const double* fresh_pos,
+                                           const double* fresh_landmarks, const int64_t* fresh_goals, float* obs,
+                                           float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
+                                           int world_length, int auto_reset, mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !goals || !comm || !actions || !obs || !rewards || !dones || !per_agent)
+        return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks || !fresh_goals)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || world_length < 1) return MAPPO_E_SHAPE;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    return launch_step(reference_step_kernel, RefArgs{s, i64(goals), i64(comm), i64(actions), i64(fresh_goals)},
+                       stream_);
 }

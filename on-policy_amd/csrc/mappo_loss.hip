@@ -285,13 +285,11 @@ extern "C" int mappo_ppo_loss_f32(const mappo_ppo_loss_t* args, mappo_stream_t s
 // step.  Sampling is torch.multinomial's own rule for one draw: argmax_i p_i / q_i with q ~ Exponential(1) -- the noise is
 // drawn by the caller from torch's generator (graph-safe philox), so the distribution is exactly the framework's.
 // One thread per row; n_actions <= 64.
-__global__ void __launch_bounds__(256) categorical_sample_kernel(const float* logits, const float* avail, const float* noise,
-                                                                 long long* actions, float* logp, long long rows, int na) {
-    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (r >= rows) return;
-    const float* lg = logits + r * na;
-    const float* av = avail ? avail + r * na : nullptr;
-    const float* q = noise + r * na;
+
+// One head of one row: the normalised logits of `lg[0..na)` (entries whose availability is 0 count as -1e10), the sampled
+// action argmax_i p_i / q_i and its log-probability.
+__device__ __forceinline__ void sample_head(const float* lg, const float* av, const float* q, int na, long long* action,
+                                            float* logp) {
     float mx = -INFINITY;
     for (int i = 0; i < na; ++i) {
         const float x = (av && av[i] == 0.f) ? -1e10f : lg[i];
@@ -315,8 +313,15 @@ __global__ void __launch_bounds__(256) categorical_sample_kernel(const float* lo
             best_l = l;
         }
     }
-    actions[r] = best;
-    logp[r] = best_l;
+    *action = best;
+    *logp = best_l;
+}
+
+__global__ void __launch_bounds__(256) categorical_sample_kernel(const float* logits, const float* avail, const float* noise,
+                                                                 long long* actions, float* logp, long long rows, int na) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    sample_head(logits + r * na, avail ? avail + r * na : nullptr, noise + r * na, na, actions + r, logp + r);
 }
 
 extern "C" int mappo_categorical_sample(const float* logits, const float* available, const float* noise, int64_t* actions,
@@ -326,5 +331,50 @@ extern "C" int mappo_categorical_sample(const float* logits, const float* availa
     hipLaunchKernelGGL(categorical_sample_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream_), logits, available, noise,
                        reinterpret_cast<long long*>(actions), log_probs, (long long)rows, n_actions);
+    return (int)hipGetLastError();
+}
+
+// K14 for a MultiDiscrete head: the sub-heads' Categorical samples of ACTLayer.forward's multi-discrete branch (reference
+// act.py:44-60: per sub-head FixedCategorical.sample / log_probs, then cat) in one launch.  The logits of all sub-heads
+// are one [rows, sum n_k] matrix; sub-head k samples with its own noise tensor [rows, n_k], which the caller draws per
+// sub-head in head order -- exactly the Exponential(1) draws of the framework's per-head torch.multinomial(p, 1) calls --
+// so actions and random stream are those of the framework path.  Log-probs stay per sub-head (not summed).
+// One thread per row; at most MAPPO_MULTI_SAMPLE_MAX_HEADS sub-heads, sum n_k <= 64.
+struct MultiSampleArgs {
+    const float* noise[MAPPO_MULTI_SAMPLE_MAX_HEADS];
+    int size[MAPPO_MULTI_SAMPLE_MAX_HEADS];
+    int heads, width;
+};
+
+__global__ void __launch_bounds__(256) multi_categorical_sample_kernel(const float* logits, MultiSampleArgs m,
+                                                                       long long* actions, float* logp, long long rows) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const float* lg = logits + r * m.width;
+    for (int h = 0; h < m.heads; ++h) {
+        const int na = m.size[h];
+        sample_head(lg, nullptr, m.noise[h] + r * na, na, actions + r * m.heads + h, logp + r * m.heads + h);
+        lg += na;
+    }
+}
+
+extern "C" int mappo_multi_categorical_sample(const float* logits, const float* const* noise, const int* head_sizes,
+                                              int num_heads, int64_t* actions, float* log_probs, int64_t rows,
+                                              mappo_stream_t stream_) {
+    if (!logits || !noise || !head_sizes || !actions || !log_probs) return MAPPO_E_NULL;
+    if (rows <= 0 || num_heads <= 0 || num_heads > MAPPO_MULTI_SAMPLE_MAX_HEADS) return MAPPO_E_SHAPE;
+    MultiSampleArgs m = {};
+    m.heads = num_heads;
+    for (int h = 0; h < num_heads; ++h) {
+        if (!noise[h]) return MAPPO_E_NULL;
+        if (head_sizes[h] <= 0) return MAPPO_E_SHAPE;
+        m.noise[h] = noise[h];
+        m.size[h] = head_sizes[h];
+        m.width += head_sizes[h];
+    }
+    if (m.width > 64) return MAPPO_E_SHAPE;
+    hipLaunchKernelGGL(multi_categorical_sample_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), logits, m, reinterpret_cast<long long*>(actions), log_probs,
+                       (long long)rows);
     return (int)hipGetLastError();
 }

@@ -201,8 +201,7 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise NativeError(
                 "libmappo_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` or `make -C on-policy_amd/csrc -f Makefile -f ../csrc_ext/ext.mk`. There is no CPU "
-                "fallback." % LIB_PATH)
+                "g.build()'` or `make -C on-policy_amd/csrc`. There is no CPU fallback." % LIB_PATH)
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)  # AttributeError here = header / library mismatch

@@ -26,10 +26,6 @@ import torch
 from onpolicy.utils.graph_capture import capturing
 
 
-# the state tensors of an env that does not declare its own (``state_names``): simple_spread's worlds
-DEFAULT_STATE_NAMES = ("pos", "vel", "landmarks", "t")
-
-
 class RolloutGraph(object):
     WARMUP = 3
 
@@ -97,9 +93,8 @@ class RolloutGraph(object):
         return (share_next, obs, rnn_a, rnn_c, actions, logp, values, rewards, masks), infos
 
     def _state_names(self):
-        """The env's state tensors that a replay advances in place: what the env declares (``state_names``), else those of
-        simple_spread's worlds."""
-        return tuple(getattr(self.r.envs, "state_names", DEFAULT_STATE_NAMES))
+        """The env's state tensors that a replay advances in place: what the env declares (``state_names``)."""
+        return tuple(self.r.envs.state_names)
 
     def _env_state(self):
         e = self.r.envs
@@ -191,8 +186,7 @@ class RolloutGraph(object):
         self.replays += 1
         self.r.buffer.insert(*self.out)
         # (a fresh lazy view of the static per-agent rewards: the previous one may have cached an older step)
-        per_agent = getattr(self.infos, "_per_agent", None)
-        return type(self.infos)(per_agent) if per_agent is not None else self.infos
+        return self.infos.fresh()
 
 
 def build(runner):
@@ -201,9 +195,9 @@ def build(runner):
     if os.environ.get("MAPPO_ROLLOUT_GRAPH", "1") == "0":
         return None
     envs = runner.envs
-    if not getattr(envs, "device_resident", False) or not hasattr(envs, "rng") or not hasattr(envs, "pos"):
-        return None
-    if not getattr(envs, "graph_safe", False):      # the step must advance its state tensors in place (K11 does)
+    # device-resident worlds (envs/mpe/particle_worlds.py) declare ``graph_safe`` (the step advances the tensors named by
+    # ``state_names`` in place: the K11 family does) and draw from their own generator ``rng``
+    if not getattr(envs, "device_resident", False) or not envs.graph_safe:
         return None
     if torch.device(runner.buffer.device).type != "cuda" or distributions.SAMPLING_RNG != "device":
         return None

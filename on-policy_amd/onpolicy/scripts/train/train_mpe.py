@@ -21,26 +21,23 @@ The reference's train_mpe_reference.sh on the device:
 import sys
 
 from onpolicy.config import get_config
+from onpolicy.envs.mpe.simple_reference import TorchSimpleReference
+from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread, VecSimpleSpread
 from onpolicy.scripts.train import _launch
 
 
-# scenarios with an in-tree device implementation (--use_device_env)
-DEVICE_SCENARIOS = ("simple_spread", "simple_reference")
+# scenarios with an in-tree device implementation (--use_device_env; row f1): the worlds are held on the policy's device
+DEVICE_ENVS = {"simple_spread": TorchSimpleSpread, "simple_reference": TorchSimpleReference}
 
 
 def make_train_env(all_args, n_threads=None, seed_offset=0, device=None):
     n = all_args.n_rollout_threads if n_threads is None else n_threads
     seed_offset += 1000 * getattr(all_args, "rollout_thread_offset", 0)      # data-parallel rank: its own worlds
-    if all_args.scenario_name == "simple_spread" and device is not None:    # worlds held on the device (row f1)
-        from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread
-        return TorchSimpleSpread(n, all_args.num_agents, all_args.num_landmarks, all_args.episode_length,
-                                 seed=all_args.seed + seed_offset, device=device)
-    if all_args.scenario_name == "simple_reference" and device is not None:     # worlds held on the device
-        from onpolicy.envs.mpe.simple_reference import TorchSimpleReference
-        return TorchSimpleReference(n, all_args.num_agents, all_args.num_landmarks, all_args.episode_length,
-                                    seed=all_args.seed + seed_offset, device=device)
+    if device is not None and all_args.scenario_name in DEVICE_ENVS:
+        return DEVICE_ENVS[all_args.scenario_name](n, all_args.num_agents, all_args.num_landmarks,
+                                                   all_args.episode_length, seed=all_args.seed + seed_offset,
+                                                   device=device)
     if all_args.scenario_name == "simple_spread":       # built in, all worlds advanced by one numpy pass
-        from onpolicy.envs.mpe.simple_spread import VecSimpleSpread
         return VecSimpleSpread(n, all_args.num_agents, all_args.num_landmarks, all_args.episode_length,
                                seed=all_args.seed + seed_offset)
     # any other scenario: one MPEEnv per worker like the reference (train_mpe.py:16-32); the scenario modules
@@ -76,8 +73,8 @@ def main(args):
     run_dir = _launch.new_run_dir(all_args, all_args.scenario_name)
     _launch.seed_everything(all_args)
     shared = all_args.share_policy and all_args.algorithm_name not in ("happo", "hatrpo")
-    if all_args.use_device_env and not (shared and all_args.scenario_name in DEVICE_SCENARIOS):
-        raise NotImplementedError("--use_device_env: simple_spread with the shared-policy runner only")
+    if all_args.use_device_env and not (shared and all_args.scenario_name in DEVICE_ENVS):
+        raise NotImplementedError("--use_device_env: %s with the shared-policy runner only" % " / ".join(DEVICE_ENVS))
     envs = make_train_env(all_args, device=device if all_args.use_device_env else None)
     eval_envs = make_train_env(all_args, all_args.n_eval_rollout_threads, 50000) if all_args.use_eval else None
     if shared:
