@@ -139,8 +139,11 @@ __global__ void __launch_bounds__(256) ppo_loss_kernel(mappo_ppo_loss_t a) {
             const float adv = a.adv[i];
             const float lo = 1.f - a.clip, hi = 1.f + a.clip;
             const float surr1 = ratio * adv;
-            const float surr2 = fminf(fmaxf(ratio, lo), hi) * adv;
-            float s = fminf(surr1, surr2);
+            // (comparisons, not fminf / fmaxf, which drop a NaN operand: torch.clamp and torch.min hand a NaN ratio on, so
+            // the policy sum of a span with a poisoned row is NaN and not the finite (1 - clip) * adv)
+            const float rc = ratio < lo ? lo : (ratio > hi ? hi : ratio);
+            const float surr2 = rc * adv;
+            float s = (surr1 < surr2 || surr1 != surr1) ? surr1 : surr2;
             const bool inside = ratio >= lo && ratio <= hi;
             float ds_dratio = (inside || surr1 < surr2) ? adv : 0.f;  // min / clamp sub-gradients as autograd takes them
             if (a.factor != nullptr) {                                 // happo_trainer.py:137-141

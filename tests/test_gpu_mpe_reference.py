@@ -72,7 +72,8 @@ def _sample_on_noise(logits, noise, sizes):
 
 
 @pytest.mark.parametrize("sizes,rows", [([5, 10], 4099), ([3, 4], 333), ([8] * 8, 1025), ([40, 23, 1], 3),
-                                        ([5, 10], 1)])
+                                        ([5, 10], 1), ([57, 7], 4099), ([1] * 8, 257), ([57, 7], 262145),
+                                        ([8] * 8, 256)])
 def test_multi_categorical_sample_kernel_vs_the_framework_rule(sizes, rows):
     """Per sub-head: log p = x - logsumexp(x), action = argmax p / q on the SAME Exponential(1) noise (torch.multinomial's
     rule for one draw), log-prob of the action; sub-heads side by side, log-probs not summed."""
@@ -91,6 +92,37 @@ def test_multi_categorical_sample_kernel_vs_the_framework_rule(sizes, rows):
     assert same.float().mean() >= 0.999
     assert bool(((actions >= 0) & (actions < torch.tensor(sizes, device=DEV))).all())
     torch.testing.assert_close(logp[same], ref_lp[same], rtol=1e-5, atol=1e-6)
+    # where an action differs it is a near-tie: in float64 the two candidates' p / q agree to 1e-5 (no wrong action can hide
+    # in the 0.1 %), and every log-prob is that of the action the kernel chose
+    for k, x in enumerate(logits.split(sizes, -1)):
+        l64 = x.double() - x.double().logsumexp(-1, keepdim=True)
+        score = l64.exp() / noise[k].double()
+        mine, best = score.gather(-1, actions[:, k:k + 1]), score.max(-1, keepdim=True).values
+        assert bool(((best - mine).abs() <= 1e-5 * best).all()), (k, sizes)
+        torch.testing.assert_close(logp[:, k:k + 1].double(), l64.gather(-1, actions[:, k:k + 1]), rtol=1e-5, atol=1e-6)
+    if sizes == [1] * 8:
+        assert float(actions.abs().max()) == 0 and float(logp.abs().max()) == 0.0       # one action: chosen, log 1
+
+
+def test_multi_categorical_sample_with_wide_logits():
+    """Logits x 30 (probabilities from 1 down to underflow) through two sub-heads that fill the 64 columns."""
+    sizes, rows = [57, 7], 4099
+    g = torch.Generator(device=DEV).manual_seed(4)
+    logits = torch.randn(rows, 64, device=DEV, generator=g) * 30.0
+    noise = [torch.empty(rows, n, device=DEV).exponential_(1.0, generator=g) for n in sizes]
+    actions, logp = _sample_on_noise(logits, noise, sizes)
+    same = 0
+    for k, x in enumerate(logits.split(sizes, -1)):
+        l64 = x.double() - x.double().logsumexp(-1, keepdim=True)
+        score = l64.exp() / noise[k].double()
+        a = actions[:, k:k + 1]
+        mine, best = score.gather(-1, a), score.max(-1, keepdim=True).values
+        assert bool(((best - mine).abs() <= 1e-5 * best).all())
+        same += int((a == score.argmax(-1, keepdim=True)).sum())
+        # (one float32 ulp of the largest logit on top of the benign tolerance: rounding logsumexp to float32)
+        torch.testing.assert_close(logp[:, k:k + 1].double(), l64.gather(-1, a), rtol=1e-5,
+                                   atol=1e-6 + 2.0 ** -23 * float(x.abs().max()))
+    assert same >= 0.999 * rows * len(sizes)
 
 
 def test_multi_categorical_sample_frequencies():
