@@ -204,7 +204,7 @@ def standardize_rows(src2d, eps=1e-5, pad=True, out=None):
     kernels take their aligned paths (direct-to-LDS weight gradient, no tail shifting) for odd observation widths;
     ``RowSource(..., width=D)`` remembers the true width."""
     rows, D = src2d.shape
-    ld = (D + 3) // 4 * 4 if pad and os.environ.get("MAPPO_PAD_STANDARDIZED", "1") != "0" else D
+    ld = (D + 3) // 4 * 4 if pad else D
     if out is None or tuple(out.shape) != (rows, ld) or out.dtype != src2d.dtype or out.device != src2d.device:
         out = torch.empty((rows, ld), dtype=src2d.dtype, device=src2d.device)       # (``out``: storage to write into again)
     _native.check(_native.lib().mappo_standardize_rows_ld(src2d.data_ptr(), rows, D, float(eps), out.data_ptr(), ld,

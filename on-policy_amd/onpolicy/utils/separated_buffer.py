@@ -63,8 +63,7 @@ class SeparatedReplayBuffer(object):
         """HAPPO's running product of the other agents' probability ratios, [T, N, k]."""
         f = self._inner._dev(factor).reshape(self.episode_length, self.n_rollout_threads, 1, -1).clone()
         self.factor = f[:, :, 0]
-        self._inner.extra_fields["factor"] = f
-        self._inner._content_version += 1     # packed sampler records are stale
+        self._inner.set_extra_field("factor", f)
 
     # -- storage: the inner buffer only checks element counts, so [N, ...] slabs go straight through
     def insert(self, share_obs, obs, rnn_states, rnn_states_critic, actions, action_log_probs, value_preds,
@@ -118,8 +117,8 @@ class SeparatedReplayBuffer(object):
             "data chunk length ({}).".format(N, T, L))
         assert data_chunks >= 2, ("need larger batch size")
         rand = inner._sampler_indices(data_chunks, mb, num_mini_batch)
-        table, stats = inner._field_table(self._adv(advantages))
-        packed = inner._pack_records(table)
+        table, stats, external = inner._field_table(self._adv(advantages))
+        packed = inner._pack_records(table, external)
         seq_table = [(name, None if is_state else src, is_state) for name, src, is_state in table]
         state_table = [(name, src if is_state else None, is_state) for name, src, is_state in table]
         steps = torch.arange(L, device=self.device)

@@ -19,6 +19,7 @@ constructor, attributes, methods and 12-tuple minibatch protocol, but
 There is no CPU implementation here: the constructor raises unless it gets a HIP device and
 ``libmappo_hip.so`` (see onpolicy/_native.py).
 """
+import collections
 import ctypes
 import os
 
@@ -47,6 +48,12 @@ class AdvantageHandle(object):
                                             self.raw.numel(), _native.stream_of(self.raw.device)),
                       "mappo_adv_normalize")
         return out
+
+
+# What ``buffer.advantages`` (and the moment partials beside it) hold: the GAE accumulator of the MAT branches or
+# ``returns - D(value_preds)``, whether D() de-normalised, and the keys (SharedReplayBuffer._key) of the fields they were
+# formed from.
+_Advantages = collections.namedtuple("_Advantages", "is_gae denormalized inputs")
 
 
 class SharedReplayBuffer(object):
@@ -137,29 +144,27 @@ class SharedReplayBuffer(object):
         self._adv_partials = torch.zeros((rows, 3), dtype=torch.float64, device=dev)
         self._adv_sums = torch.zeros(3, dtype=torch.float64, device=dev)
         self._adv_stats = torch.zeros(2, **f32)
-        self._content_version = 0  # bumped by every method that writes buffer fields
+        # ONE staleness mechanism for every cache below: a write counter per field name, bumped by _wrote() after a checked
+        # launch of this class's kernels (they write through raw pointers); _key() joins it with the tensor's address and
+        # torch's own version counter (in-place torch writes).  A cache records the keys of the fields it was computed from.
+        self._writes = collections.defaultdict(int)
         self._whole_batch = self._whole_batch_key = None    # the one-minibatch tuple of feed_forward_generator, see there
         self._whole_batch_versions = ()
         self.whole_batch_reuses = 0       # epochs that were handed the cached tuple (tests assert the route)
         self._std_rows = {}        # field name -> (key, row-standardised copy) for the fused trunk kernels
         self._std_keep = {}        # field name -> storage of the last copy, kept across train() calls when small (below)
-        self._obs_writes = {"share_obs": 0, "obs": 0}   # slab writes of this class's kernels into the observation fields
+        self._records = self._records_key = None    # the packed sampler records (_pack_records)
+        self._identity_idx = None  # 0 .. n - 1, the device sampler's single slice that takes every sample (_sampler_indices)
         # MAPPO_STANDARDIZE_AT_INSERT (default on): once a train() has asked for the row-standardised copy of an
         # observation field, the copy stays resident and insert / chooseinsert / after_update keep it current slab by slab
         # (_write_slabs), so a train() finds it ready instead of re-standardising the whole field (VERDICT r5 "next" #4a)
         self._std_at_insert = os.environ.get("MAPPO_STANDARDIZE_AT_INSERT", "1") != "0"
         self.std_slab_launches = self.std_full_passes = 0      # (tests / bench.py: which of the two ran)
-        # MAPPO_PINNED_INSERT=1: host inputs of insert() go through one pinned staging buffer + one async H2D copy.
-        # Off by default: measured at the north star (tools/pcie_insert_bench.py, 57 MB per step) the single-threaded
-        # memcpy into the staging buffer makes it slower (1.88 ms per step, 30 GB/s) than one pageable .to(device) per
-        # field (1.11 ms, 51 GB/s), whose staging the runtime pipelines internally
-        self._pinned_insert = os.environ.get("MAPPO_PINNED_INSERT", "0") == "1"
-        self._host_stage = None
-        self._adv_fresh = False   # advantages/moments match the current returns & value_preds
-        self._adv_denormalized = False   # ... and were formed as returns - D(value_preds)
-        self._adv_is_gae = False         # ... or are the GAE accumulator of the MAT branches
-        self._stats_fresh = False
+        self._adv = None          # _Advantages: what self.advantages holds; None: nothing valid
+        self._moments_of = None   # key of the advantages that _adv_sums / _adv_stats were reduced from
         self._events = None       # kernel name -> [(start, end, algorithmic bytes)], see profile_kernels
+        self._gae_profiled = 0    # GAE launches seen while profiling (they alternate between two ways of timing)
+        self._gae_dispatch = []   # (slot, algorithmic bytes) of the launches timed by the kernel's own timestamps
 
     # ------------------------------------------------------------------ helpers
     @staticmethod
@@ -216,7 +221,7 @@ class SharedReplayBuffer(object):
                 out[name] = (len(evs), sum(ms) / len(ms), sum(n for _, _, n in evs) / len(evs))
         import ctypes
         ms, nb = [], []
-        for slot, nbytes in getattr(self, "_gae_dispatch", []):
+        for slot, nbytes in self._gae_dispatch:
             v = ctypes.c_float(0.0)
             if self._lib.mappo_gae_timed_launch_ms(slot, ctypes.byref(v)) == 0:     # (a launch without the hook: skipped)
                 ms.append(float(v.value))
@@ -236,56 +241,38 @@ class SharedReplayBuffer(object):
             x = torch.as_tensor(np.asarray(x, dtype=np.float32))
         x = x.detach()
         if x.device != self.device or x.dtype != torch.float32:
+            # host values of insert(): one pageable copy per field, whose staging the runtime pipelines internally (1.11 ms per
+            # north-star step of 57 MB, 51 GB/s; one pinned staging buffer filled by a single-threaded memcpy + one
+            # asynchronous copy took 1.88 ms, 30 GB/s: profiles/r02_pcie_insert.json)
             x = x.to(device=self.device, dtype=torch.float32, non_blocking=True)
         return x.contiguous()
 
-    # ---- host -> HBM staging of a rollout step (the caller side of the boundary: envs that live on the host)
-    def _stage_host_values(self, pairs):
-        """Values that arrive as host arrays (numpy / CPU tensors / lists) are packed into ONE page-locked staging
-        buffer and cross PCIe as ONE asynchronous copy on the buffer's stream, instead of one synchronous pageable
-        ``.to(device)`` per field; the fused slab write (K2) that follows reads them from a device staging area.
-        ``insert()`` then returns as soon as the host memcpy into the staging buffer is done: the DMA (57 MB per step at
-        the north star) overlaps the next env step.  Two staging buffers alternate; an event per buffer keeps a step
-        from overwriting data whose copy is still in flight.  -> pairs with host values replaced by device views."""
-        # (host values only: a tensor that lives on another GPU takes the ordinary device-to-device path of _dev())
-        host = [(i, v) for i, (_, v) in enumerate(pairs) if not (torch.is_tensor(v) and v.device.type != "cpu")]
-        if not host or not self._pinned_insert:
-            return pairs
-        arrays = []
-        for i, v in host:
-            a = v.detach().numpy() if torch.is_tensor(v) else np.asarray(v)
-            arrays.append((i, a))
-        total = sum(a.size for _, a in arrays)
-        st = self._host_stage
-        if st is None or st["pin"][0].numel() < total:
-            st = {"pin": [torch.empty(total, dtype=torch.float32, pin_memory=True) for _ in range(2)],
-                  "dev": [torch.empty(total, dtype=torch.float32, device=self.device) for _ in range(2)],
-                  "done": [None, None], "turn": 0}
-            self._host_stage = st
-        k = st["turn"]
-        st["turn"] = 1 - k
-        if st["done"][k] is not None:
-            st["done"][k].synchronize()                 # the copy issued two inserts ago (long finished in practice)
-        pin_np = st["pin"][k].numpy()
-        out, off = list(pairs), 0
-        for i, a in arrays:
-            np.copyto(pin_np[off:off + a.size].reshape(a.shape), a, casting="unsafe")      # cast to float32 on the way
-            out[i] = (pairs[i][0], st["dev"][k][off:off + a.size].view(a.shape))
-            off += a.size
-        st["dev"][k][:off].copy_(st["pin"][k][:off], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        st["done"][k] = ev
-        return out
+    def _key(self, name, tensor):
+        """What field ``name``, held in ``tensor``, is unchanged under: the same storage, no write of this class's kernels
+        (_wrote) and no in-place torch write (runners do ``buffer.obs[0] = ...``) since."""
+        return (tensor.data_ptr(), self._writes[name], tensor._version)
 
-    def _write_slabs(self, pairs, obs_slabs=()):
-        """One mappo_slab_copy launch for [(dst_view, value), ...] (K2).  ``obs_slabs``: (field name, time index) of the
-        pairs that write a slab of share_obs / obs -- the resident row-standardised copy of that field (if a train() made
-        one) is brought up to date for just that slab."""
-        if self.device.type == "cuda":
-            pairs = self._stage_host_values(pairs)
-        keep, slabs, srcs = [], [], {}
-        for dst, value in pairs:
+    def _wrote(self, *names):
+        """This class's kernels just wrote these fields.  Called after the launch has passed _native.check."""
+        for name in names:
+            self._writes[name] += 1
+
+    def set_extra_field(self, name, tensor):
+        """Register a [T, N, A, k] tensor that the samplers gather after the 12 standard fields.  (Counted as a write: a
+        fresh tensor may land on the address of the one it replaces.)"""
+        self.extra_fields[name] = tensor
+        self._wrote(name)
+
+    def _write_slabs(self, writes):
+        """One mappo_slab_copy launch for [(field name, time index, value), ...] (K2).  Where a slab of share_obs / obs is
+        written and the resident row-standardised copy of that field (if a train() made one) was current until now, the same
+        launch recomputes that slab of the copy from the value being written and the copy stays current (row T is not part
+        of the copy: nothing to recompute).  A copy that was already stale stays stale and is rebuilt by the next train()."""
+        T, na = self.episode_length, self.n_rollout_threads * self.num_agents
+        keep, slabs, std, resident = [], [], [], {}
+        for name, t, value in writes:
+            field = getattr(self, name)
+            dst = field[t]
             src = self._dev(value)
             if src.numel() != dst.numel() and src.numel() * dst.shape[-1] == dst.numel():
                 # numpy assignment semantics of the reference (shared_buffer.py:107-121): a [.., 1] value is
@@ -296,20 +283,19 @@ class SharedReplayBuffer(object):
                                  % (src.numel(), dst.numel(), tuple(dst.shape)))
             assert dst.is_contiguous()
             keep.append(src)
-            srcs[dst.data_ptr()] = src
-            slabs.append((src.data_ptr(), dst.data_ptr(), dst.numel()))
-        arr = (_native.Slab * len(slabs))(*[_native.Slab(s, d, n) for s, d, n in slabs])
-        # the slabs of the resident standardised copies that follow (same launch: K2's extra workgroups, csrc/mappo_copy.hip)
-        std = []
-        for name, t in obs_slabs:
-            hit = self._obs_slab_written(name, t)
-            if hit is not None:
-                na = self.n_rollout_threads * self.num_agents
-                field = getattr(self, name)
-                src = srcs[field[t].data_ptr()]             # the value being written, not the buffer slab
-                D = int(field.shape[-1])
-                out = hit[t * na:(t + 1) * na]
-                std.append(_native.StdSlab(src.data_ptr(), out.data_ptr(), na, D, int(out.shape[1]), 1e-5))
+            slabs.append(_native.Slab(src.data_ptr(), dst.data_ptr(), dst.numel()))
+            hit = self._std_rows.get(name)
+            if self._std_at_insert and hit is not None and hit[0] == self._key(name, field):
+                resident[name] = hit[1]
+                if t < T:
+                    # the slab of the resident copy (same launch: K2's extra workgroups, csrc/mappo_copy.hip), from the
+                    # value being written, not the buffer slab
+                    out = hit[1][t * na:(t + 1) * na]
+                    std.append(_native.StdSlab(src.data_ptr(), out.data_ptr(), na, dst.numel() // na,     # (all trailing axes)
+                                               int(out.shape[1]), 1e-5))
+        arr = (_native.Slab * len(slabs))(*slabs)
+        for name, copy in resident.items():
+            self._std_rows[name] = (None, copy)     # not current again before the launch has passed its check
         if std:
             sarr = (_native.StdSlab * len(std))(*std)
             _native.check(self._lib.mappo_slab_copy_std(arr, len(slabs), sarr, len(std), self._stream()),
@@ -317,24 +303,9 @@ class SharedReplayBuffer(object):
             self.std_slab_launches += len(std)      # (slabs standardised; they ride in K2's launch)
         else:
             _native.check(self._lib.mappo_slab_copy(arr, len(slabs), self._stream()), "mappo_slab_copy")
-        self._content_version += 1
-
-    def _obs_key(self, name):
-        """What a standardised copy of field ``name`` is valid for: this class's slab writes + in-place torch writes."""
-        return (name, self._obs_writes[name], getattr(self, name)._version)
-
-    def _obs_slab_written(self, name, t):
-        """Slab ``t`` of observation field ``name`` is being rewritten by K2.  A resident standardised copy that was current
-        until now stays current: -> the copy, whose slab t the same launch recomputes from the value being written (row T is
-        not part of the copy: -> None, nothing to do).  A copy that was already stale stays stale (-> None) and is rebuilt by
-        the next train()."""
-        hit = self._std_rows.get(name)
-        current = self._std_at_insert and hit is not None and hit[0] == self._obs_key(name)
-        self._obs_writes[name] += 1
-        if not current:
-            return None
-        self._std_rows[name] = (self._obs_key(name), hit[1])
-        return hit[1] if t < self.episode_length else None
+        self._wrote(*[name for name, _, _ in writes])
+        for name, copy in resident.items():
+            self._std_rows[name] = (self._key(name, getattr(self, name)), copy)
 
     # ------------------------------------------------------------------ storage
     def insert(self, share_obs, obs, rnn_states_actor, rnn_states_critic, actions, action_log_probs,
@@ -343,21 +314,20 @@ class SharedReplayBuffer(object):
         row ``step + 1``, action-like fields in row ``step``.  Values may be numpy arrays or tensors
         on any device, shaped [N, A, ...]."""
         s = self.step
-        pairs = [(self.share_obs[s + 1], share_obs), (self.obs[s + 1], obs),
-                 (self.actions[s], actions), (self.action_log_probs[s], action_log_probs),
-                 (self.value_preds[s], value_preds), (self.rewards[s], rewards),
-                 (self.masks[s + 1], masks)]
+        writes = [("share_obs", s + 1, share_obs), ("obs", s + 1, obs),
+                  ("actions", s, actions), ("action_log_probs", s, action_log_probs),
+                  ("value_preds", s, value_preds), ("rewards", s, rewards),
+                  ("masks", s + 1, masks)]
         if self._recurrent:
-            pairs += [(self.rnn_states[s + 1], rnn_states_actor),
-                      (self.rnn_states_critic[s + 1], rnn_states_critic)]
+            writes += [("rnn_states", s + 1, rnn_states_actor),
+                       ("rnn_states_critic", s + 1, rnn_states_critic)]
         if bad_masks is not None:
-            pairs.append((self.bad_masks[s + 1], bad_masks))
+            writes.append(("bad_masks", s + 1, bad_masks))
         if active_masks is not None:
-            pairs.append((self.active_masks[s + 1], active_masks))
+            writes.append(("active_masks", s + 1, active_masks))
         if available_actions is not None:
-            pairs.append((self.available_actions[s + 1], available_actions))
-        self._write_slabs(pairs, obs_slabs=(("share_obs", s + 1), ("obs", s + 1)))
-        self._adv_fresh = False
+            writes.append(("available_actions", s + 1, available_actions))
+        self._write_slabs(writes)
         self.step = (s + 1) % self.episode_length
 
     def chooseinsert(self, share_obs, obs, rnn_states, rnn_states_critic, actions, action_log_probs,
@@ -365,38 +335,37 @@ class SharedReplayBuffer(object):
         """Turn-based (Hanabi) insert (reference shared_buffer.py:125-158): observations, active masks
         and available actions go to row ``step`` instead of ``step + 1``."""
         s = self.step
-        pairs = [(self.share_obs[s], share_obs), (self.obs[s], obs),
-                 (self.actions[s], actions), (self.action_log_probs[s], action_log_probs),
-                 (self.value_preds[s], value_preds), (self.rewards[s], rewards),
-                 (self.masks[s + 1], masks)]
+        writes = [("share_obs", s, share_obs), ("obs", s, obs),
+                  ("actions", s, actions), ("action_log_probs", s, action_log_probs),
+                  ("value_preds", s, value_preds), ("rewards", s, rewards),
+                  ("masks", s + 1, masks)]
         if self._recurrent:
-            pairs += [(self.rnn_states[s + 1], rnn_states), (self.rnn_states_critic[s + 1], rnn_states_critic)]
+            writes += [("rnn_states", s + 1, rnn_states), ("rnn_states_critic", s + 1, rnn_states_critic)]
         if bad_masks is not None:
-            pairs.append((self.bad_masks[s + 1], bad_masks))
+            writes.append(("bad_masks", s + 1, bad_masks))
         if active_masks is not None:
-            pairs.append((self.active_masks[s], active_masks))
+            writes.append(("active_masks", s, active_masks))
         if available_actions is not None:
-            pairs.append((self.available_actions[s], available_actions))
-        self._write_slabs(pairs, obs_slabs=(("share_obs", s), ("obs", s)))
-        self._adv_fresh = False
+            writes.append(("available_actions", s, available_actions))
+        self._write_slabs(writes)
         self.step = (s + 1) % self.episode_length
 
     def after_update(self):
         """Row T becomes row 0 of the next rollout (reference shared_buffer.py:160-170)."""
-        fields = [self.share_obs, self.obs, self.masks, self.bad_masks, self.active_masks]
+        names = ["share_obs", "obs", "masks", "bad_masks", "active_masks"]
         if self._recurrent:
-            fields += [self.rnn_states, self.rnn_states_critic]
+            names += ["rnn_states", "rnn_states_critic"]
         if self.available_actions is not None:
-            fields.append(self.available_actions)
-        self._write_slabs([(f[0], f[-1]) for f in fields], obs_slabs=(("share_obs", 0), ("obs", 0)))
+            names.append("available_actions")
+        self._write_slabs([(name, 0, getattr(self, name)[-1]) for name in names])
         self._release_update_scratch()
 
     def chooseafter_update(self):
         """Hanabi variant (reference shared_buffer.py:172-177)."""
-        fields = [self.masks, self.bad_masks]
+        names = ["masks", "bad_masks"]
         if self._recurrent:
-            fields += [self.rnn_states, self.rnn_states_critic]
-        self._write_slabs([(f[0], f[-1]) for f in fields])
+            names += ["rnn_states", "rnn_states_critic"]
+        self._write_slabs([(name, 0, getattr(self, name)[-1]) for name in names])
         self._release_update_scratch()
 
     def _release_update_scratch(self):
@@ -411,7 +380,7 @@ class SharedReplayBuffer(object):
         for name, (_, t) in list(self._std_rows.items()):
             small = t.numel() * t.element_size() <= limit
             if small and self._std_at_insert:
-                continue                    # stays in _std_rows: resident, kept current by _obs_slab_written
+                continue                    # stays in _std_rows: resident, kept current by _write_slabs
             if small:
                 self._std_keep[name] = t
             del self._std_rows[name]
@@ -462,6 +431,7 @@ class SharedReplayBuffer(object):
             raise ValueError("next_value has %d elements, expected %d" % (nv.numel(), N * A))
         denorm = self._denorm_scalars(value_normalizer) if _scan_denorm else None
         p = _native.ptr
+        self._adv = None
         if self.algo in ("mat", "mat_dec") and self._use_gae and not self._use_proper_time_limits:
             # transformer branches (reference shared_buffer.py:222-232, :241-251): the advantages are the
             # GAE accumulator itself and, without a normaliser, the TD error uses the agent-mean value
@@ -473,14 +443,10 @@ class SharedReplayBuffer(object):
                 self._stream())
             self._timed_end(ev)
             _native.check(code, "mappo_gae_mat_f32")
-            self._content_version += 1
-            self._adv_fresh = True
-            self._adv_denormalized = bool(self._use_popart or self._use_valuenorm)   # = what MATTrainer reads
-            self._adv_is_gae = True
-            self._stats_fresh = False
-            self._adv_inputs = self._adv_input_versions()
+            self._wrote("returns", "advantages")
+            # (denormalized: = what MATTrainer reads)
+            self._adv = _Advantages(True, bool(self._use_popart or self._use_valuenorm), self._adv_input_keys())
             return
-        self._adv_is_gae = False
         # algorithmic bytes: r, v, m reads + returns write (16 B) + advantages write + active read
         # (+8 B) [+ bad_masks read 4 B] per (t, n, a) element  
         # while profiling (bench.py), the launches are timed ALTERNATELY by an event pair recorded around the launch (what
@@ -491,12 +457,12 @@ class SharedReplayBuffer(object):
         nbytes = (24 + (4 if self._use_proper_time_limits else 0)) * T * N * A
         ev = None
         if self._events is not None and not torch.cuda.is_current_stream_capturing():
-            self._gae_profiled = getattr(self, "_gae_profiled", 0) + 1
+            self._gae_profiled += 1
             if self._gae_profiled % 2 == 0:
                 torch.cuda._sleep(250000)           # (as in _timed: the kernel starts from a filled queue)
                 slot = self._lib.mappo_gae_time_next_launch()
                 if slot >= 0:
-                    self._gae_dispatch = (getattr(self, "_gae_dispatch", []) + [(slot, nbytes)])[-64:]
+                    self._gae_dispatch = (self._gae_dispatch + [(slot, nbytes)])[-64:]
             else:
                 ev = self._timed("mappo_gae_f32", nbytes, settle=True)
         code = self._lib.mappo_gae_f32(
@@ -506,17 +472,13 @@ class SharedReplayBuffer(object):
             T, N * A, float(self.gamma), float(self.gae_lambda), self._gae_flags(denorm), self._stream())
         self._timed_end(ev)
         _native.check(code, "mappo_gae_f32")
-        self._content_version += 1
-        self._adv_fresh = True
-        self._adv_denormalized = denorm is not None      # what the fused advantages subtracted
-        self._stats_fresh = False
-        self._adv_inputs = self._adv_input_versions()
+        self._wrote("returns", "advantages")
+        self._adv = _Advantages(False, denorm is not None, self._adv_input_keys())    # (what the fused advantages subtracted)
 
-    def _adv_input_versions(self):
-        """In-place torch writes to the fields the fused advantages / moments were formed from bump these
-        counters (runners do edit them between compute_returns and train, e.g. ``active_masks[-1] = ...``);
-        this class's own kernels write through raw pointers and leave them alone."""
-        return (self.returns._version, self.value_preds._version, self.active_masks._version)
+    def _adv_input_keys(self):
+        """Keys of the fields the fused advantages / moments are formed from (runners do edit them in place between
+        compute_returns and train, e.g. ``active_masks[-1] = ...``; insert / after_update write them through K2)."""
+        return tuple(self._key(name, getattr(self, name)) for name in ("returns", "value_preds", "active_masks"))
 
     def normalized_advantages(self, value_normalizer=None, all_reduce=None, denormalize=None):
         """What the prologue of the reference's ``R_MAPPO.train`` computes (r_mappo.py:179-187), as an
@@ -533,30 +495,30 @@ class SharedReplayBuffer(object):
         want = flagged if denormalize is None else bool(denormalize)
         if want and not flagged:
             raise ValueError("denormalize=True needs a buffer built with use_popart / use_valuenorm")
-        if self._adv_fresh and getattr(self, "_adv_inputs", None) != self._adv_input_versions():
-            self._adv_fresh = False        # returns / value_preds / active_masks were edited in place since
-        if self._adv_fresh and self._adv_is_gae and denormalize is None:
+        adv = self._adv
+        if adv is not None and adv.inputs != self._adv_input_keys():
+            adv = None        # returns / value_preds / active_masks were written since
+        if adv is not None and adv.is_gae and denormalize is None:
             pass       # MAT: buffer.advantages is what the trainer normalises (mat_trainer.py:160-164)
-        elif not self._adv_fresh or self._adv_denormalized != want:
-            self._adv_is_gae = False
+        elif adv is None or adv.denormalized != want:
             denorm = self._denorm_scalars(value_normalizer) if want else None
-            self._adv_denormalized = want
+            self._adv = None
             code = self._lib.mappo_advantages_f32(p(self.returns), p(self.value_preds), p(denorm),
                                                   p(self.active_masks), p(self.advantages),
                                                   p(self._adv_partials), T, N * A, self._stream())
             _native.check(code, "mappo_advantages_f32")
-            self._content_version += 1
-            self._adv_fresh = True
-            self._stats_fresh = False
-            self._adv_inputs = self._adv_input_versions()
-        if not self._stats_fresh or all_reduce is not None:
+            self._wrote("advantages")
+            self._adv = _Advantages(False, want, self._adv_input_keys())
+        summed = self._key("advantages", self.advantages)
+        if self._moments_of != summed or all_reduce is not None:
+            self._moments_of = None
             _native.check(self._lib.mappo_adv_reduce(p(self._adv_partials), self._partial_rows,
                                                      p(self._adv_sums), self._stream()), "mappo_adv_reduce")
             if all_reduce is not None:
                 all_reduce(self._adv_sums)
             _native.check(self._lib.mappo_adv_stats(p(self._adv_sums), p(self._adv_stats), self._stream()),
                           "mappo_adv_stats")
-            self._stats_fresh = True
+            self._moments_of = summed
         return AdvantageHandle(self.advantages, self._adv_stats, self)
 
     # ------------------------------------------------------------------ samplers
@@ -577,7 +539,7 @@ class SharedReplayBuffer(object):
         if n_mb == 1 and mb == n:
             # one slice that takes every sample: K10 would emit 0 .. n - 1 (slices come out in ascending order) whatever
             # the keys -- three launches per epoch saved (the generator's draw above still happens: same random stream)
-            if getattr(self, "_identity_idx", None) is None or self._identity_idx.numel() != n:
+            if self._identity_idx is None or self._identity_idx.numel() != n:
                 self._identity_idx = torch.arange(n, dtype=torch.int64, device=self.device)
             return self._identity_idx
         idx = torch.empty(n_mb * mb, dtype=torch.int64, device=self.device)
@@ -591,7 +553,8 @@ class SharedReplayBuffer(object):
         device sampler no longer sorts, there is nothing to overlap."""
 
     def _field_table(self, advantages):
-        """(name, source tensor whose rows are gathered, trailing shape, first_only, adv mode)."""
+        """-> ([(name, source tensor whose rows are gathered, is an RNN state), ...], the advantages' (mean, std) or None,
+        whether ``advantages`` is an array of the caller's instead of this buffer's)."""
         T = self.episode_length
         table = [
             ("share_obs", self.share_obs, False),
@@ -605,8 +568,7 @@ class SharedReplayBuffer(object):
             ("active_masks", self.active_masks, False),
             ("action_log_probs", self.action_log_probs, False),
         ]
-        stats = None
-        self._adv_external = False
+        stats, external = None, False
         if advantages is None:
             adv = None
         elif isinstance(advantages, AdvantageHandle):
@@ -615,7 +577,7 @@ class SharedReplayBuffer(object):
             # the reference's protocol: an array / tensor the caller owns.  It is gathered as a field of its
             # own and never enters the packed records: the upload below is a temporary whose address and
             # version counter can repeat across calls, so it cannot key the record cache
-            self._adv_external = True
+            external = True
             adv = self._dev(advantages)
             if adv.numel() != T * self.n_rollout_threads * self.num_agents:
                 raise ValueError("advantages has the wrong number of elements")
@@ -623,7 +585,7 @@ class SharedReplayBuffer(object):
         table.append(("available_actions", self.available_actions, False))
         for name, tensor in self.extra_fields.items():
             table.append((name, tensor, False))
-        return table, stats
+        return table, stats, external
 
     supports_standardized_obs = True   # generators take standardize_obs=True (see feed_forward_generator)
 
@@ -648,18 +610,16 @@ class SharedReplayBuffer(object):
     _NARROW = 8
     _MAX_RECORD = 32
 
-    def _pack_records(self, table):
+    def _pack_records(self, table, adv_external):
         """Pack the narrow fields (per-sample scalars, available_actions, ...) into one
         [T*N*A, RW] record array (mappo_pack_records) -> (records, RW, {name: (offset, width)}).
         Done once per generator call, i.e. per epoch: ~1 GB of traffic against ~47 GB per gather."""
         T, N, A = self.episode_length, self.n_rollout_threads, self.num_agents
-        layout, fields, off, versions = {}, [], 0, []
-        if os.environ.get("MAPPO_PACK_RECORDS", "1") == "0":
-            return None, 0, {}
+        layout, fields, off, keys = {}, [], 0, []
         for name, src, is_state in table:
             if src is None or is_state or name in ("share_obs", "obs"):
                 continue   # observations / RNN states keep their own (wide or standardising) path
-            if name == "advantages" and self._adv_external:
+            if name == "advantages" and adv_external:
                 continue
             tail = tuple(src.shape[3:])
             width = int(np.prod(tail)) if tail else 1
@@ -667,7 +627,7 @@ class SharedReplayBuffer(object):
                 continue
             layout[name] = (off, width)
             fields.append(_native.RecordField(src.data_ptr(), None, width, off, 0, 0))
-            versions.append(src._version)      # in-place torch writes to the field (setitem, copy_, ...)
+            keys.append(self._key(name, src))
             off += width
         if not fields:
             return None, 0, {}
@@ -681,13 +641,13 @@ class SharedReplayBuffer(object):
             while rw < off:      # random permutations: 16 / 32 / 64 / 128-byte records never straddle more sectors than needed
                 rw *= 2
         rows = T * N * A
-        # the packed fields only change when the buffer is written -- by this class's kernels
-        # (_content_version) or by in-place torch ops on the field tensors (tensor._version): within
-        # one train() every epoch reuses the records of the first
-        key = (self._content_version, tuple(versions), tuple((f.src, f.width, f.offset) for f in fields))
-        if getattr(self, "_records_key", None) == key:
+        # the packed fields only change when they are written (_key): within one train() every epoch reuses the records of
+        # the first
+        key = (tuple(keys), tuple((f.width, f.offset) for f in fields), rw)
+        if self._records_key == key:
             return self._records, rw, layout
-        if getattr(self, "_records", None) is None or self._records.numel() < rows * rw:
+        self._records_key = None
+        if self._records is None or self._records.numel() < rows * rw:
             self._records = torch.empty(rows * rw, dtype=torch.float32, device=self.device)
         arr = (_native.RecordField * len(fields))(*fields)
         _native.check(self._lib.mappo_pack_records(arr, len(fields), self._records.data_ptr(), rw, rows,
@@ -706,7 +666,7 @@ class SharedReplayBuffer(object):
         rows = field[:T].reshape(T * self.n_rollout_threads * self.num_agents, -1)
         if not standardized:
             return rows
-        key = self._obs_key(name)
+        key = self._key(name, field)
         hit = self._std_rows.get(name)
         if hit is None or hit[0] != key:
             out = hit[1] if hit is not None else self._std_keep.pop(name, None)
@@ -720,7 +680,7 @@ class SharedReplayBuffer(object):
         the SAME device code that keeps single slabs current inside K2's launch (mappo_slab_copy_std with no copy slabs), so
         that a slab and the full pass agree bit for bit."""
         n, D = rows2d.shape
-        ld = (D + 3) // 4 * 4 if os.environ.get("MAPPO_PAD_STANDARDIZED", "1") != "0" else D
+        ld = (D + 3) // 4 * 4
         if out is None or tuple(out.shape) != (n, ld) or out.dtype != rows2d.dtype or out.device != rows2d.device:
             out = torch.empty((n, ld), dtype=rows2d.dtype, device=rows2d.device)
         assert rows2d.is_contiguous()
@@ -795,23 +755,26 @@ class SharedReplayBuffer(object):
 
     # One minibatch that takes every sample (chunk) in memory order -- the device sampler's single slice: the 12-tuple is
     # the same in every epoch of a train() -- nothing writes the buffer in between -- so it is gathered once and handed out
-    # again (nine of ten gathers and row tables per north-star step saved).  Keyed on the buffer's content (the record
-    # cache's key + the fields' tensor versions), dropped with the other scratch of an update.
+    # again (nine of ten gathers and row tables per north-star step saved).  Keyed on the keys of the table's fields (_key)
+    # and the route's parameters, dropped with the other scratch of an update.
     # CONTRACT: the tensors of such a tuple are SHARED between the epochs of one train() -- read-only for the caller.  (The
     # reference's generators yield independent copies, shared_buffer.py:379-396; they still do here for the reference
     # protocol -- an external ``advantages`` array never takes this route -- and for several minibatches per epoch.)  An
     # in-place edit of a yielded tensor is detected through its version counter and the batch is gathered again, so a
     # trainer that does edit them gets the reference's semantics at the price of the gather.
-    def _whole_batch_ok(self, rand, packed):
-        return rand is getattr(self, "_identity_idx", None) and packed[0] is not None and not self._adv_external
+    def _whole_batch_ok(self, rand, packed, adv_external):
+        return rand is self._identity_idx and packed[0] is not None and not adv_external
+
+    def _whole_batch_cache_key(self, form, table, stats, chunk_len, standardize_obs, lazy_obs):
+        return (form, chunk_len, bool(standardize_obs), bool(lazy_obs), None if stats is None else stats.data_ptr(),
+                tuple(self._key(name, src) for name, src, _ in table if src is not None))
 
     @staticmethod
     def _output_versions(outs):
         return tuple(t._version for t in outs if torch.is_tensor(t))
 
     def _whole_batch_tuple(self, table, stats, rand, mb, chunk_len, standardize_obs, lazy_obs, packed):
-        key = (self._records_key, chunk_len, bool(standardize_obs), bool(lazy_obs), None if stats is None else stats.data_ptr(),
-               tuple((src.data_ptr(), src._version) for _, src, _ in table if src is not None))
+        key = self._whole_batch_cache_key("copies", table, stats, chunk_len, standardize_obs, lazy_obs)
         if self._whole_batch_key == key and self._output_versions(self._whole_batch) == self._whole_batch_versions:
             self.whole_batch_reuses += 1
             return self._whole_batch
@@ -830,14 +793,13 @@ class SharedReplayBuffer(object):
     # _whole_batch_tuple.  With standardize_obs alone (networks that take tensors: hidden 512) the observation elements of the
     # tuple are the resident standardised copies themselves -- rows padded to 16 bytes, which K15's aligned loads want anyway
     # (Hanabi's 1285 / 1385-wide rows: first-layer forward 4.51 -> 4.16 ms, no standardising gather).
-    def _whole_batch_views_ok(self, rand, mb, batch_size):
-        return rand is getattr(self, "_identity_idx", None) and mb == batch_size and not self._adv_external \
+    def _whole_batch_views_ok(self, rand, mb, batch_size, adv_external):
+        return rand is self._identity_idx and mb == batch_size and not adv_external \
             and os.environ.get("MAPPO_WHOLE_BATCH_VIEWS", "1") != "0"
 
     def _whole_batch_views(self, table, stats, rand, mb, standardize_obs, lazy_obs=True):
         T = self.episode_length
-        key = ("views", self._content_version, bool(standardize_obs), bool(lazy_obs), None if stats is None else stats.data_ptr(),
-               tuple((src.data_ptr(), src._version) for _, src, _ in table if src is not None))
+        key = self._whole_batch_cache_key("views", table, stats, None, standardize_obs, lazy_obs)
         if self._whole_batch_key == key:
             self.whole_batch_reuses += 1
             return self._whole_batch
@@ -898,14 +860,15 @@ class SharedReplayBuffer(object):
                 "".format(N, T, A, batch_size, num_mini_batch))
             mini_batch_size = batch_size // num_mini_batch
         rand = self._sampler_indices(batch_size, mini_batch_size, num_mini_batch)
-        table, stats = self._field_table(advantages)
-        if num_mini_batch == 1 and (lazy_obs or standardize_obs) and self._whole_batch_views_ok(rand, mini_batch_size, batch_size) \
+        table, stats, external = self._field_table(advantages)
+        if num_mini_batch == 1 and (lazy_obs or standardize_obs) \
+                and self._whole_batch_views_ok(rand, mini_batch_size, batch_size, external) \
                 and (lazy_obs or self.can_standardize_obs()):
             # (standardize_obs / lazy_obs are this implementation's extensions of the protocol: only its own trainer passes them)
             yield self._whole_batch_views(table, stats, rand, mini_batch_size, standardize_obs, lazy_obs)
             return
-        packed = self._pack_records(table)
-        if num_mini_batch == 1 and self._whole_batch_ok(rand, packed):
+        packed = self._pack_records(table, external)
+        if num_mini_batch == 1 and self._whole_batch_ok(rand, packed, external):
             yield self._whole_batch_tuple(table, stats, rand, mini_batch_size, None, standardize_obs, lazy_obs, packed)
             return
         for i in range(num_mini_batch):
@@ -922,9 +885,9 @@ class SharedReplayBuffer(object):
         data_chunks = batch_size // data_chunk_length
         mini_batch_size = data_chunks // num_mini_batch
         rand = self._sampler_indices(data_chunks, mini_batch_size, num_mini_batch)
-        table, stats = self._field_table(advantages)
-        packed = self._pack_records(table)
-        if num_mini_batch == 1 and mini_batch_size == data_chunks and self._whole_batch_ok(rand, packed):
+        table, stats, external = self._field_table(advantages)
+        packed = self._pack_records(table, external)
+        if num_mini_batch == 1 and mini_batch_size == data_chunks and self._whole_batch_ok(rand, packed, external):
             yield self._whole_batch_tuple(table, stats, rand, mini_batch_size, data_chunk_length, standardize_obs, lazy_obs,
                                           packed)
             return
@@ -948,8 +911,8 @@ class SharedReplayBuffer(object):
         else:       # the reference's last, shorter slice (shared_buffer.py:417): a full permutation
             perm = torch.randperm(batch_size).to(self.device) if self._sampler_rng == "host" \
                 else torch.randperm(batch_size, device=self.device)
-        table, stats = self._field_table(advantages)
-        packed = self._pack_records(table)
+        table, stats, external = self._field_table(advantages)
+        packed = self._pack_records(table, external)
         for start in range(0, batch_size, num_envs_per_batch):
             idx = perm[start:start + num_envs_per_batch]
             yield self._gather(table, stats, idx, idx.numel(), chunk_len=T, standardize_obs=standardize_obs,
@@ -970,8 +933,8 @@ class SharedReplayBuffer(object):
                 "".format(N, T, batch_size, num_mini_batch))
             mini_batch_size = batch_size // num_mini_batch
         rand = self._sampler_indices(batch_size, mini_batch_size, num_mini_batch)
-        table, stats = self._field_table(advantages)
-        packed = self._pack_records(table)
+        table, stats, external = self._field_table(advantages)
+        packed = self._pack_records(table, external)
         agents = torch.arange(A, device=self.device)
         for i in range(num_mini_batch):
             idx = rand[i * mini_batch_size:(i + 1) * mini_batch_size]

@@ -729,6 +729,55 @@ def test_gae_properties_at_scale():
     torch.testing.assert_close(sa, sb, rtol=1e-6, atol=1e-7)
 
 
+def _host_moments(buf, vn):
+    """nan-aware mean / std of ``returns[:-1] - D(value_preds[:-1])`` over the buffer's current ``active_masks[:-1]``
+    (reference r_mappo.py:179-187), float64 on the host; D() with the scalars the kernel itself reads."""
+    sigma, mu = [float(x) for x in vn.denorm_scalars().cpu().numpy()]
+    adv = buf.returns[:-1].cpu().numpy().astype(np.float64) \
+        - (buf.value_preds[:-1].cpu().numpy().astype(np.float64) * sigma + mu)
+    adv[buf.active_masks[:-1].cpu().numpy() == 0.0] = np.nan
+    return np.nanmean(adv), np.nanstd(adv)
+
+
+def test_advantage_moments_follow_after_update():
+    """after_update() writes row 0 of active_masks (through K2, raw pointers): the advantages' moments handed out after it
+    are counted over the new row, not served from before."""
+    T, N, A = 50, 33, 4
+    args = make_args(episode_length=T, n_rollout_threads=N)
+    arrays = _random_case(T, N, A, 57, _dev())
+    arrays["active_masks"][-1] = 1.0 - arrays["active_masks"][0]          # row T differs from row 0 everywhere
+    buf = _buffer(args, A)
+    load_into(buf, arrays)
+    vn = _vn([0.7e-4, 3.1e-4, 2.5e-5])
+    buf.compute_returns(arrays["next_value"], vn)
+    before = buf.normalized_advantages(vn).stats.cpu().numpy()
+    np.testing.assert_allclose(before, _host_moments(buf, vn), rtol=1e-6, atol=1e-7)
+    buf.after_update()
+    assert torch.equal(buf.active_masks[0], buf.active_masks[-1])
+    after = buf.normalized_advantages(vn).stats.cpu().numpy()
+    expect = _host_moments(buf, vn)
+    print("moments before %r, after %r, float64 over the current masks %r" % (before, after, expect))
+    np.testing.assert_allclose(after, expect, rtol=1e-6, atol=1e-7)
+
+
+def test_update_factor_twice_yields_the_second_factor():
+    """A second update_factor() replaces the first: its clone may land on the storage the first one gave up (same address,
+    a fresh version counter), and the samplers must still hand out the new values."""
+    from onpolicy.utils.separated_buffer import SeparatedReplayBuffer
+    T, N = 6, 4
+    args = make_args(episode_length=T, n_rollout_threads=N, hidden_size=8)
+    buf = SeparatedReplayBuffer(args, Box((5,)), Box((9,)), Discrete(4), device=_dev())
+    adv = np.zeros((T, N, 1), np.float32)
+    rng = np.random.default_rng(2)
+    for _ in range(2):
+        factor = rng.standard_normal((T, N, 1)).astype(np.float32)
+        buf.update_factor(factor)
+        sample = next(iter(buf.feed_forward_generator(adv, 1)))
+        assert len(sample) == 13
+        got = np.sort(sample[12].cpu().numpy().reshape(-1))
+        np.testing.assert_array_equal(got, np.sort(factor.reshape(-1)))
+
+
 def test_packed_record_cache_invalidation():
     """The per-epoch record pack is cached; any write to a packed field -- through the buffer's
     kernels or through plain torch in-place ops -- must invalidate it."""

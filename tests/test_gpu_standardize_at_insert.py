@@ -1,10 +1,11 @@
 """-m gpu: the row-standardised observation copies the fused trunk kernels (K9) read stay resident after a train() and are
-kept current slab by slab by insert / chooseinsert / after_update (utils/shared_buffer.py: _obs_slab_written; VERDICT r5
+kept current slab by slab by insert / chooseinsert / after_update (utils/shared_buffer.py: _write_slabs; VERDICT r5
 "next" #4a), inside K2's own launch (mappo_slab_copy_std) -- bit-identical to standardising the whole field again (the full
 pass runs the same device code), and within float32 rounding of the float64 definition; never stale:
 
 * slab writes of this class's kernels update exactly the slab they wrote (and nothing for row T, which is not part of the copy);
 * in-place torch writes to the field (runners do ``buffer.obs[0] = ...``) are seen through the version counter -> full pass;
+* a slab write whose launch fails its check leaves the copy stale -> full pass;
 * a whole rollout + train() loop ends with the weights of the same loop under MAPPO_STANDARDIZE_AT_INSERT=0, bit for bit.
 """
 import numpy as np
@@ -76,6 +77,36 @@ def test_an_in_place_torch_write_forces_the_full_pass():
     torch.testing.assert_close(got, _fresh(buf, "obs"), rtol=0, atol=0)
     torch.testing.assert_close(buf._obs_rows("share_obs", True), _fresh(buf, "share_obs"), rtol=0, atol=0)
     assert buf.std_full_passes == 3
+
+
+class _FailingSlabStd(object):
+    """The library handle with a ``mappo_slab_copy_std`` that launches nothing and returns an error code."""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        if name == "mappo_slab_copy_std":
+            return lambda *a: 1
+        return getattr(self._lib, name)
+
+
+@pytest.mark.parametrize("name", ["share_obs", "obs"])
+def test_a_failed_slab_launch_leaves_the_copy_stale(name):
+    from onpolicy._native import NativeError
+    args, buf = _buffer()
+    buf.share_obs.normal_()
+    buf.obs.normal_()
+    buf._obs_rows(name, True)
+    lib = buf._lib
+    buf._lib = _FailingSlabStd(lib)
+    with pytest.raises(NativeError):
+        buf.insert(*_step_values(np.random.default_rng(7)))
+    buf._lib = lib
+    passes = buf.std_full_passes
+    got = buf._obs_rows(name, True)
+    assert buf.std_full_passes == passes + 1
+    torch.testing.assert_close(got, _fresh(buf, name), rtol=0, atol=0)
 
 
 def _loop(monkeypatch, at_insert):
