@@ -20,6 +20,7 @@ lives and when the host looks at it:
 
 The forward / backward maths of the actor and critic stays in PyTorch.
 """
+import collections
 import os
 
 import numpy as np
@@ -32,6 +33,46 @@ from onpolicy.algorithms.utils.util import check
 from onpolicy.utils import dist as mdist
 from onpolicy.algorithms.utils import fused_loss
 from onpolicy.algorithms.utils.fused_mlp import RowSource
+
+
+# One minibatch, fields in the order the reference's generators yield them (shared_buffer.py:336-338; HAPPO's
+# separated_buffer.py:227 appends the factor).  The buffers keep yielding plain tuples; R_MAPPO._minibatch names them.
+Minibatch = collections.namedtuple("Minibatch", (
+    "share_obs", "obs", "rnn_states", "rnn_states_critic", "actions", "value_preds", "returns", "masks", "active_masks",
+    "old_action_log_probs", "adv_targ", "available_actions", "factor"), defaults=(None,))
+# the columns ppo_update converts to float32 tensors on the trainer's device (reference r_mappo.py:113-117, happo_trainer.py:120)
+_LOSS_COLUMNS = ("value_preds", "returns", "active_masks", "old_action_log_probs", "adv_targ", "factor")
+
+
+class _Spans(collections.namedtuple("_Spans", "spans chunk_len n_chunks")):
+    """What R_MAPPO._row_spans plans for a minibatch: the spans [lo, hi) it is evaluated in -- of rows (chunk_len None) or,
+    for a recurrent minibatch of ``n_chunks`` chunks, of whole chunks of ``chunk_len`` steps."""
+
+    def cut(self, mb, lo, hi):
+        """The minibatch of span [lo, hi); a single span is the minibatch itself, nothing sliced."""
+        if len(self.spans) == 1:
+            return mb
+        return Minibatch(*(self._cut(x, lo, hi) for x in mb))
+
+    def _cut(self, x, lo, hi):
+        if x is None:
+            return x
+        if isinstance(x, RowSource):
+            return x.rows_slice(lo, hi)
+        if self.chunk_len is None or x.shape[0] == self.n_chunks:   # row spans / per-chunk RNN states
+            return x[lo:hi]
+        tail = x.shape[1:]                                          # [L * mb, ...] with row l * mb + j
+        return x.reshape(self.chunk_len, self.n_chunks, *tail)[:, lo:hi].reshape(self.chunk_len * (hi - lo), *tail)
+
+
+class _Prologue(object):
+    """What the loss of a minibatch needs from outside the rows of the span it is looking at (R_MAPPO._prologue)."""
+    __slots__ = (
+        "w_actor", "w_critic",  # data-parallel weights of the two losses: local / global denominators, 1.0 in one process
+        "inv", "scale4",        # fused loss: 1 / the global (policy, value) denominators that K7 takes, and what turns its
+        "sums",                 # four float64 sums (accumulated over the spans) into this rank's means
+        "feed",                 # (returns, global moments or None) the value normaliser is still to be fed; None: nothing
+        "whole")                # several framework-loss spans: (rows, sum of active masks) of the whole minibatch; else None
 
 
 class R_MAPPO():
@@ -164,154 +205,115 @@ class R_MAPPO():
     # row spans; gradients accumulate, so the update is the same full-minibatch update.
     MAX_TENSOR_ELEMENTS = 1 << 30
 
-    def _row_spans(self, sample):
-        """-> (spans, chunk_len).  Feed-forward minibatches (chunk_len None) are cut into row spans
-        [lo, hi); recurrent ones ([L * mb, ...] sequence fields with row l * mb + j and [mb, ...] RNN states)
-        into spans of whole chunks j in [lo, hi), every span keeping all L steps of its chunks."""
-        rows = sample[10].shape[0] if sample[10] is not None else sample[5].shape[0]
+    def _minibatch(self, sample):
+        """What a generator yields (a 12- or 13-tuple of host arrays, device tensors and RowSources) -> ``Minibatch``: the
+        columns the loss arithmetic reads become float32 tensors on the trainer's device (reference r_mappo.py:113-117),
+        the factor is kept only by trainers that use one.  (A ``Minibatch`` is taken as well: what is converted stays.)"""
+        mb = Minibatch(*sample)
+        mb = mb._replace(factor=mb.factor if self._use_factor else None)
+        return mb._replace(**{k: check(getattr(mb, k)).to(**self.tpdv) for k in _LOSS_COLUMNS
+                              if getattr(mb, k) is not None})
+
+    def _row_spans(self, mb):
+        """-> _Spans.  Feed-forward minibatches (chunk_len None) are cut into row spans [lo, hi); recurrent ones
+        ([L * mb, ...] sequence fields with row l * mb + j and [mb, ...] RNN states) into spans of whole chunks j in
+        [lo, hi), every span keeping all L steps of its chunks."""
+        rows = mb.adv_targ.shape[0]
         # a RowSource is never materialised by the fused trunk: what the networks write per row are 64-wide activations
         widest = max((64 if isinstance(t, RowSource) else int(np.prod(t.shape[1:])))
-                     for t in (sample[0], sample[1]) if t is not None)
+                     for t in (mb.share_obs, mb.obs) if t is not None)
         cap = max(1, self.MAX_TENSOR_ELEMENTS // max(1, widest))
-        recurrent = sample[2] is not None and sample[2].shape[0] != rows
         if rows <= cap:
-            return [(0, rows)], None
-        if recurrent:
-            mb = sample[2].shape[0]
-            chunk_len = rows // mb
-            units, cap = mb, max(1, cap // chunk_len)
-        else:
-            chunk_len, units = None, rows
+            return _Spans([(0, rows)], None, None)
+        chunk_len, units = None, rows
+        if mb.rnn_states is not None and mb.rnn_states.shape[0] != rows:        # recurrent
+            units = mb.rnn_states.shape[0]
+            chunk_len = rows // units
+            cap = max(1, cap // chunk_len)
         n = -(-units // cap)
         step = -(-units // n)
-        return [(lo, min(units, lo + step)) for lo in range(0, units, step)], chunk_len
+        return _Spans([(lo, min(units, lo + step)) for lo in range(0, units, step)], chunk_len, units)
+
+    def _prologue(self, mb, plan, fused, scales=None):
+        """-> _Prologue of a minibatch.  ``scales`` is the float32 [8] tensor of ``DataParallel.minibatch_scales`` when
+        the caller (update_graph.py) already holds it; the fused loss on a HIP device asks for it here; a data-parallel
+        job without it spends one small collective (``minibatch_stats``); everything else is local arithmetic."""
+        pro = _Prologue()
+        masked = (self._use_policy_active_masks, self._use_value_active_masks)
+        normalized = (self._use_popart or self._use_valuenorm) and self._updates_normalizer
+        # fused loss on a HIP device: denominators, their reciprocals and the returns' batch moments in three launches
+        if scales is None and fused:
+            scales = self.dp.minibatch_scales(mb.active_masks, mb.returns, *masked)
+        # In a data-parallel job each rank's loss is a mean over ITS minibatch; weighting it by
+        # (local denominator / global denominator) makes the all-reduced gradient the gradient of
+        # the global-batch mean.  Weights are exactly 1 for world size 1.
+        pro.w_actor = pro.w_critic = 1.0
+        moments = None          # (of the returns over the GLOBAL minibatch; None: the normaliser takes the local minibatch's)
+        if scales is not None and normalized:
+            moments = (scales[6:7], scales[7:8])
+        elif scales is None and self.dp.active:     # one small collective for the loss denominators and the normaliser moments
+            pro.w_actor, pro.w_critic, moments = self.dp.minibatch_stats(mb.active_masks, mb.returns, *masked)
+        pro.feed = (mb.returns, moments) if normalized else None
+        rows = mb.adv_targ.shape[0]
+        pro.whole = (rows, mb.active_masks.sum()) if len(plan.spans) > 1 and not fused else None
+        pro.inv = pro.scale4 = pro.sums = None
+        if fused:
+            # Nothing below may touch the host: a Python scalar turned into a device tensor (torch.as_tensor(1.0, device=...))
+            # is a blocking copy that drains the stream once per update -- the ~40 small launches up to the first trunk
+            # kernel then run at launch latency instead of from a filled queue (0.5 ms per update at a 512-thread shard).
+            f32 = dict(dtype=torch.float32, device=mb.adv_targ.device)
+            if scales is not None:      # DataParallel.minibatch_scales: [inv (2) | scale of the four sums (4) | moments (2)]
+                pro.inv, pro.scale4 = scales[0:2], scales[2:6]
+            else:
+                n_rows = torch.full((), float(rows), **f32)
+                active_total = mb.active_masks.sum() if any(masked) else n_rows
+                # [1 / policy denominator, 1 / value denominator, 1 / rows] of THIS rank's minibatch
+                inv3 = 1.0 / torch.stack([active_total if masked[0] else n_rows, active_total if masked[1] else n_rows, n_rows])
+                pro.inv = inv3[:2]
+                # data-parallel weights are local / global denominators, so this is 1 / the GLOBAL denominators
+                # (they are tensors then; the 1.0 of a single process needs no multiply)
+                if torch.is_tensor(pro.w_actor) or torch.is_tensor(pro.w_critic):
+                    pro.inv = (pro.inv * torch.stack([torch.as_tensor(pro.w_actor, **f32).reshape(()),
+                                                      torch.as_tensor(pro.w_critic, **f32).reshape(())])).contiguous()
+                pro.scale4 = torch.stack([inv3[0], inv3[0], inv3[1], inv3[2]])
+            pro.sums = torch.zeros(4, dtype=torch.float64, device=mb.adv_targ.device)
+        return pro
+
+    # The normaliser is fed once per minibatch, AFTER the first forward pass and before the loss -- the reference's
+    # order (r_mappo.py:120 evaluate_actions, then :65 update inside cal_value_loss).  It matters under PopArt, whose
+    # update rescales the value head the forward pass runs through.  ``pro.feed`` is what the update will be fed; the
+    # first span's call consumes it.
+    # (A minibatch cut into several row spans -- MAX_TENSOR_ELEMENTS, unfused routes only -- evaluates span 1 before the
+    # update and the others after it; under PopArt, whose update rescales v_out, that deviates from a single pass by
+    # the one EMA step (beta = 0.99999).  The fused trunk route only cuts above 2^30 / 64 = 16.7 M rows, _row_spans.)
+    def _feed_normalizer(self, pro):
+        if pro.feed is not None:
+            feed, pro.feed = pro.feed, None
+            self._normalizer_update(*feed)
 
     def ppo_update(self, sample, update_actor=True, _front_only=False, _scales=None):
         """One actor step and one critic step on a minibatch (reference r_mappo.py:91-169).
         -> (value_loss, critic_grad_norm, policy_loss, dist_entropy, actor_grad_norm, imp_weights).
         (``_front_only`` / ``_scales``: update_graph.py captures everything up to the gradients as one graph and hands the
         scalar prologue in as a static tensor.)"""
-        share_obs_batch, obs_batch, rnn_states_batch, rnn_states_critic_batch, actions_batch, \
-            value_preds_batch, return_batch, masks_batch, active_masks_batch, old_action_log_probs_batch, \
-            adv_targ, available_actions_batch = sample[:12]
-        factor_batch = check(sample[12]).to(**self.tpdv) if (self._use_factor and len(sample) > 12) else None
-
-        old_action_log_probs_batch = check(old_action_log_probs_batch).to(**self.tpdv)
-        adv_targ = check(adv_targ).to(**self.tpdv)
-        value_preds_batch = check(value_preds_batch).to(**self.tpdv)
-        return_batch = check(return_batch).to(**self.tpdv)
-        active_masks_batch = check(active_masks_batch).to(**self.tpdv)
-
-        spans, chunk_len = self._row_spans(sample)
-        rows = adv_targ.shape[0]
-        # In a data-parallel job each rank's loss is a mean over ITS minibatch; weighting it by
-        # (local denominator / global denominator) makes the all-reduced gradient the gradient of
-        # the global-batch mean.  Weights are exactly 1 for world size 1.
-        normalized = (self._use_popart or self._use_valuenorm) and self._updates_normalizer
-        # The normaliser is fed once per minibatch, AFTER the first forward pass and before the loss -- the
-        # reference's order (r_mappo.py:120 evaluate_actions, then :65 update inside cal_value_loss).  It matters
-        # under PopArt, whose update rescales the value head the forward pass runs through.  ``pending`` is what
-        # the update will be fed: None = nothing to do, () = the local minibatch, (mean, mean_sq) = global moments.
-        # (A minibatch cut into several row spans -- MAX_TENSOR_ELEMENTS, unfused routes only -- evaluates span 1 before the
-        # update and the others after it; under PopArt, whose update rescales v_out, that deviates from a single pass by
-        # the one EMA step (beta = 0.99999).  The fused trunk route only cuts above 2^30 / 64 = 16.7 M rows, _row_spans.)
-        pending = () if normalized else None
-        fused = self._fused_loss and adv_targ.is_cuda and actions_batch is not None
-        # fused loss on a HIP device: denominators, their reciprocals and the returns' batch moments in three launches
-        if _scales is not None:
-            scales = _scales
-        else:
-            scales = self.dp.minibatch_scales(active_masks_batch, return_batch, self._use_policy_active_masks,
-                                              self._use_value_active_masks) if fused else None
-        w_actor = w_critic = 1.0
-        if scales is not None:
-            if normalized:
-                pending = (scales[6:7], scales[7:8])
-        elif self.dp.active:    # one small collective for the loss denominators and the normaliser moments
-            w_actor, w_critic, moments = self.dp.minibatch_stats(
-                active_masks_batch, return_batch, self._use_policy_active_masks, self._use_value_active_masks)
-            if normalized:
-                pending = moments
+        mb = self._minibatch(sample)
+        fused = self._fused_loss and mb.adv_targ.is_cuda and mb.actions is not None
+        if fused:       # K7 reads the actions and the availability mask as float32 columns too
+            mb = mb._replace(**{k: check(getattr(mb, k)).to(mb.adv_targ.device, torch.float32)
+                                for k in ("actions", "available_actions") if getattr(mb, k) is not None})
+        plan = self._row_spans(mb)
+        pro = self._prologue(mb, plan, fused, _scales)
 
         self.dp.zero_grad(self.policy.actor_optimizer, self.policy.critic_optimizer)
 
-        def feed_normalizer():
-            nonlocal pending
-            if pending is not None:
-                self._normalizer_update(return_batch, pending or None)
-                pending = None
-
-        single = len(spans) == 1
-
-        n_chunks = rows // chunk_len if chunk_len else None
-
-        def cut(x, lo, hi):
-            """The part of a minibatch tensor that belongs to span [lo, hi)."""
-            if x is None or single:
-                return x
-            if isinstance(x, RowSource):
-                return x.rows_slice(lo, hi)
-            if chunk_len is None or x.shape[0] == n_chunks:        # row spans / per-chunk RNN states
-                return x[lo:hi]
-            tail = x.shape[1:]                                      # [L * mb, ...] with row l * mb + j
-            return x.reshape(chunk_len, n_chunks, *tail)[:, lo:hi].reshape(chunk_len * (hi - lo), *tail)
-
-        value_loss = policy_loss = dist_entropy = None
-        ratios = []
-        if fused:
-            value_loss, policy_loss, dist_entropy, imp_weights = self._fused_spans(
-                spans, cut, (share_obs_batch, obs_batch, rnn_states_batch, rnn_states_critic_batch, actions_batch,
-                             value_preds_batch, return_batch, masks_batch, active_masks_batch,
-                             old_action_log_probs_batch, adv_targ, available_actions_batch, factor_batch),
-                w_actor, w_critic, feed_normalizer, update_actor, scales)
-        for lo, hi in ([] if fused else spans):
-            am = cut(active_masks_batch, lo, hi)
-            values, action_log_probs, entropy = self.policy.evaluate_actions(
-                cut(share_obs_batch, lo, hi), cut(obs_batch, lo, hi), cut(rnn_states_batch, lo, hi),
-                cut(rnn_states_critic_batch, lo, hi), cut(actions_batch, lo, hi), cut(masks_batch, lo, hi),
-                cut(available_actions_batch, lo, hi), am, **self._eval_kwargs())
-
-            # clipped surrogate (r_mappo.py:129-139)
-            adv_span = cut(adv_targ, lo, hi)
-            imp_weights = self._ratio(action_log_probs, cut(old_action_log_probs_batch, lo, hi))
-            surr1 = imp_weights * adv_span
-            surr2 = torch.clamp(imp_weights, 1.0 - self.clip_param, 1.0 + self.clip_param) * adv_span
-            surr = torch.min(surr1, surr2)
-            if factor_batch is not None:
-                surr = cut(factor_batch, lo, hi) * surr                            # happo_trainer.py:137-141
-            per_sample = -torch.sum(surr, dim=-1, keepdim=True)
-            if self._use_policy_active_masks:
-                p_loss = (per_sample * am).sum() / am.sum()
-            else:
-                p_loss = per_sample.mean()
-            feed_normalizer()
-            v_loss = self._value_loss(values, cut(value_preds_batch, lo, hi), cut(return_batch, lo, hi), am,
-                                      update_normalizer=False)
-
-            # span weights: this span's share of the minibatch denominators (exactly 1 for one span)
-            if len(spans) == 1:
-                sw_actor = sw_critic = 1.0
-            else:
-                frac_rows = float(am.shape[0]) / rows
-                frac_active = am.sum() / active_masks_batch.sum()
-                sw_actor = frac_active if self._use_policy_active_masks else frac_rows
-                sw_critic = frac_active if self._use_value_active_masks else frac_rows
-
-            if update_actor:
-                ((p_loss - entropy * self.entropy_coef) * (sw_actor * w_actor)).backward()
-            (v_loss * self.value_loss_coef * (sw_critic * w_critic)).backward()
-
-            if len(spans) == 1:
-                value_loss, policy_loss, dist_entropy = v_loss, p_loss, entropy
-            else:
-                acc = lambda tot, x, w: x.detach() * w if tot is None else tot + x.detach() * w
-                value_loss = acc(value_loss, v_loss, sw_critic)
-                policy_loss = acc(policy_loss, p_loss, sw_actor)
-                dist_entropy = acc(dist_entropy, entropy, sw_actor)
-            ratios.append(imp_weights.detach() if len(spans) > 1 else imp_weights)
-            del values, action_log_probs, entropy, surr1, surr2, surr, per_sample, p_loss, v_loss
-
-        if not fused:
+        span = self._fused_span if fused else self._framework_span
+        shares = [span(plan.cut(mb, lo, hi), pro, update_actor) for lo, hi in plan.spans]
+        if fused:       # sums = [policy loss, entropy, value loss, ratio] numerators -> local means, one launch
+            means = pro.sums.float() * pro.scale4
+            value_loss, policy_loss, dist_entropy, imp_weights = means[2], means[0], means[1], means[3]
+        else:           # (one span: its own live tensors, nothing added)
+            v, p, e, ratios = zip(*shares)
+            value_loss, policy_loss, dist_entropy = (sum(x[1:], x[0]) for x in (v, p, e))
             imp_weights = ratios[0] if len(ratios) == 1 else torch.cat(ratios, 0)
         if _front_only:         # (update_graph.py: the gradient exchange and the optimiser steps follow separately)
             return value_loss, policy_loss, dist_entropy, imp_weights
@@ -319,6 +321,68 @@ class R_MAPPO():
         self.dp.all_reduce_grads()  # no-op for world size 1
         actor_grad_norm, critic_grad_norm = self._update_back(update_actor)
         return value_loss, critic_grad_norm, policy_loss, dist_entropy, actor_grad_norm, imp_weights
+
+    def _framework_span(self, mb, pro, update_actor):
+        """One span of ppo_update through the framework's ops: evaluate_actions, the clipped surrogate, the value loss and
+        one backward per network.  -> this span's share of (value_loss, policy_loss, dist_entropy) and its ratios."""
+        am = mb.active_masks
+        values, action_log_probs, entropy = self.policy.evaluate_actions(
+            mb.share_obs, mb.obs, mb.rnn_states, mb.rnn_states_critic, mb.actions, mb.masks, mb.available_actions, am,
+            **self._eval_kwargs())
+
+        # clipped surrogate (r_mappo.py:129-139)
+        imp_weights = self._ratio(action_log_probs, mb.old_action_log_probs)
+        surr1 = imp_weights * mb.adv_targ
+        surr2 = torch.clamp(imp_weights, 1.0 - self.clip_param, 1.0 + self.clip_param) * mb.adv_targ
+        surr = torch.min(surr1, surr2)
+        if mb.factor is not None:
+            surr = mb.factor * surr                                             # happo_trainer.py:137-141
+        per_sample = -torch.sum(surr, dim=-1, keepdim=True)
+        if self._use_policy_active_masks:
+            p_loss = (per_sample * am).sum() / am.sum()
+        else:
+            p_loss = per_sample.mean()
+        self._feed_normalizer(pro)
+        v_loss = self._value_loss(values, mb.value_preds, mb.returns, am, update_normalizer=False)
+
+        # span weights: this span's share of the minibatch denominators (exactly 1 for one span, which hands back its
+        # live tensors)
+        if pro.whole is None:
+            sw_actor = sw_critic = 1.0
+            share = v_loss, p_loss, entropy, imp_weights
+        else:
+            rows, active_total = pro.whole
+            frac_rows = float(am.shape[0]) / rows
+            frac_active = am.sum() / active_total
+            sw_actor = frac_active if self._use_policy_active_masks else frac_rows
+            sw_critic = frac_active if self._use_value_active_masks else frac_rows
+            share = v_loss.detach() * sw_critic, p_loss.detach() * sw_actor, entropy.detach() * sw_actor, imp_weights.detach()
+
+        if update_actor:
+            ((p_loss - entropy * self.entropy_coef) * (sw_actor * pro.w_actor)).backward()
+        (v_loss * self.value_loss_coef * (sw_critic * pro.w_critic)).backward()
+        return share
+
+    def _fused_span(self, mb, pro, update_actor):
+        """One span of ppo_update through the fused loss kernel (K7): one forward to the head's logits / the critic's
+        values, one ``mappo_ppo_loss_f32`` launch that evaluates the loss and its gradient and adds the span's numerators
+        of the four logged means to ``pro.sums``, one backward from those gradients."""
+        values, logits = self.policy.evaluate_logits(mb.share_obs, mb.obs, mb.rnn_states, mb.rnn_states_critic, mb.masks,
+                                                     **self._eval_kwargs())
+        self._feed_normalizer(pro)
+        normalized = self._use_popart or self._use_valuenorm
+        norm = self.value_normalizer.denorm_scalars().to(values.device, torch.float32).contiguous() if normalized else None
+        dlogits, dvalues = fused_loss.ppo_loss(
+            logits, mb.available_actions, mb.actions, mb.old_action_log_probs, mb.adv_targ, mb.active_masks, mb.factor,
+            values, mb.value_preds, mb.returns, norm, pro.inv, pro.sums,
+            clip=self.clip_param, huber_delta=self.huber_delta, entropy_coef=self.entropy_coef,
+            value_loss_coef=self.value_loss_coef, use_huber=self._use_huber_loss,
+            use_clipped_value_loss=self._use_clipped_value_loss,
+            policy_active_masks=self._use_policy_active_masks, value_active_masks=self._use_value_active_masks)
+        if update_actor:
+            torch.autograd.backward([logits, values], [dlogits, dvalues])
+        else:
+            values.backward(dvalues)
 
     def _update_back(self, update_actor, lr_devices=(None, None)):
         """Clipping + optimiser step of both networks on the (all-reduced) gradients -> (actor, critic) gradient norms."""
@@ -344,62 +408,6 @@ class R_MAPPO():
         if step:
             optimizer.step()
         return norm
-
-    def _fused_spans(self, spans, cut, tensors, w_actor, w_critic, feed_normalizer, update_actor, scales=None):
-        """The span loop of ppo_update through the fused loss kernel (K7): per span one forward to the
-        head's logits / the critic's values, one ``mappo_ppo_loss_f32`` launch that evaluates the loss and
-        its gradient, one backward from those gradients.  -> (value_loss, policy_loss, dist_entropy,
-        mean ratio) as device scalars."""
-        share_obs, obs, rnn_a, rnn_c, actions, value_preds, returns, masks, active, old_logp, adv, avail, factor = tensors
-        dev, rows = adv.device, adv.shape[0]
-        f32 = dict(dtype=torch.float32, device=dev)
-        actions = check(actions).to(**f32)
-        avail = None if avail is None else check(avail).to(**f32)
-        # Nothing below may touch the host: a Python scalar turned into a device tensor (torch.as_tensor(1.0, device=...))
-        # is a blocking copy that drains the stream once per update -- the ~40 small launches up to the first trunk
-        # kernel then run at launch latency instead of from a filled queue (0.5 ms per update at a 512-thread shard).
-        if scales is not None:      # DataParallel.minibatch_scales: [inv (2) | scale of the four sums (4) | moments (2)]
-            inv, scale4 = scales[0:2], scales[2:6]
-        else:
-            n_rows = torch.full((), float(rows), **f32)
-            masked = self._use_policy_active_masks or self._use_value_active_masks
-            active_total = active.sum() if masked else n_rows
-            # [1 / policy denominator, 1 / value denominator, 1 / rows] of THIS rank's minibatch
-            inv3 = 1.0 / torch.stack([active_total if self._use_policy_active_masks else n_rows,
-                                      active_total if self._use_value_active_masks else n_rows, n_rows])
-            inv_local = inv3[:2]
-            # data-parallel weights are local / global denominators, so this is 1 / the GLOBAL denominators
-            if torch.is_tensor(w_actor) or torch.is_tensor(w_critic):
-                inv = (inv_local * torch.stack([torch.as_tensor(w_actor, **f32).reshape(()),
-                                                torch.as_tensor(w_critic, **f32).reshape(())])).contiguous()
-            elif w_actor == 1.0 and w_critic == 1.0:
-                inv = inv_local
-            else:
-                inv = torch.stack([inv_local[0] * float(w_actor), inv_local[1] * float(w_critic)])
-            scale4 = torch.stack([inv3[0], inv3[0], inv3[1], inv3[2]])
-        sums = torch.zeros(4, dtype=torch.float64, device=dev)
-        normalized = self._use_popart or self._use_valuenorm
-        for lo, hi in spans:
-            values, logits = self.policy.evaluate_logits(
-                cut(share_obs, lo, hi), cut(obs, lo, hi), cut(rnn_a, lo, hi), cut(rnn_c, lo, hi), cut(masks, lo, hi),
-                **self._eval_kwargs())
-            feed_normalizer()           # reference order: forward, normaliser update, loss (r_mappo.py:120-66)
-            norm = self.value_normalizer.denorm_scalars().to(**f32).contiguous() if normalized else None
-            dlogits, dvalues = fused_loss.ppo_loss(
-                logits, cut(avail, lo, hi), cut(actions, lo, hi), cut(old_logp, lo, hi), cut(adv, lo, hi),
-                cut(active, lo, hi), cut(factor, lo, hi), values, cut(value_preds, lo, hi), cut(returns, lo, hi), norm, inv,
-                sums, clip=self.clip_param, huber_delta=self.huber_delta, entropy_coef=self.entropy_coef,
-                value_loss_coef=self.value_loss_coef, use_huber=self._use_huber_loss,
-                use_clipped_value_loss=self._use_clipped_value_loss,
-                policy_active_masks=self._use_policy_active_masks, value_active_masks=self._use_value_active_masks)
-            if update_actor:
-                torch.autograd.backward([logits, values], [dlogits, dvalues])
-            else:
-                values.backward(dvalues)
-            del values, logits, dlogits, dvalues
-        # sums = [policy loss, entropy, value loss, ratio] numerators -> local means, one launch
-        means = sums.float() * scale4
-        return means[2], means[0], means[1], means[3]
 
     def _fused_trunks(self, fold):
         """Both networks' trunks qualify for the fused kernels (K9) and expect the kind of rows the sampler would hand
@@ -531,8 +539,10 @@ class R_MAPPO():
         cur = next(it, None)
         while cur is not None:
             nxt = next(it, None)
-            if nxt is not None and torch.is_tensor(nxt[8]) and torch.is_tensor(nxt[6]) and nxt[8].is_cuda:
-                self.dp.begin_scales(nxt[8], nxt[6], self._use_policy_active_masks, self._use_value_active_masks)
+            ahead = None if nxt is None else Minibatch(*nxt)    # (named, not converted: host minibatches get no prologue ahead)
+            am, ret = (None, None) if ahead is None else (ahead.active_masks, ahead.returns)
+            if torch.is_tensor(am) and torch.is_tensor(ret) and am.is_cuda:
+                self.dp.begin_scales(am, ret, self._use_policy_active_masks, self._use_value_active_masks)
             yield cur
             cur = nxt
 

@@ -46,8 +46,33 @@ import os
 
 import torch
 
+from onpolicy.algorithms.r_mappo.r_mappo import Minibatch
 from onpolicy.algorithms.utils.fused_mlp import RowSource, matrix_arithmetic_of
 from onpolicy.utils.graph_capture import capturing
+
+
+class _Entry(object):
+    """What ``UpdateGraph`` holds per signature.  ``state`` is "warm" (seen once, the eager update was the warm-up), "ready"
+    (captured, replays) or "failed" (its capture failed: the shape stays eager); everything else is set by the capture."""
+    __slots__ = (
+        "state",
+        "static", "inputs",         # the Minibatch the graphs read (clones of the captured one) and its device tensors
+        "loaded",                   # ((id, version) of the tensors the static inputs hold a copy of, those tensors)
+        "scales", "scales_src",     # static copy of the scalar prologue, and the tensor it was last copied from
+        "lr", "lr_val",             # per optimiser: the learning rate in device memory (K13 reads it there) and on the host
+        "front",                    # graph: zero_grad .. backward of both networks (one process: the optimiser steps too)
+        "back", "front_grads",      # multi-GPU: graph of clip + Adam, after the eager exchange of the front's gradients
+        "front_done",               # multi-GPU: the front already ran for the minibatch that triggered the capture
+        "grads", "out")             # what a caller finds in .grad after an update; the six tensors ppo_update returns
+
+    def __init__(self, state="warm"):
+        for name in self.__slots__:
+            setattr(self, name, None)
+        self.state = state
+
+    def fail(self):
+        """Let go of everything captured; the signature stays eager from here on."""
+        self.__init__("failed")
 
 
 class UpdateGraph(object):
@@ -90,11 +115,10 @@ class UpdateGraph(object):
                 parts.append(("view", x.data_ptr(), tuple(x.shape), tuple(x.stride()), x.dtype))
             else:
                 return None, 0
-        rows = sample[10].shape[0]
+        rows = sample.adv_targ.shape[0]
         if rows > self.max_rows or not update_actor:
             return None, 0          # (update_actor = False leaves the actor without gradients: the PyTorch optimiser path)
-        spans, _ = t._row_spans(sample)
-        if len(spans) != 1:
+        if len(t._row_spans(sample).spans) != 1:
             return None, 0
         arith = tuple(matrix_arithmetic_of(m) for net in (t.policy.actor, t.policy.critic) for m in net.modules()
                       if hasattr(m, "matrix_arithmetic"))
@@ -137,23 +161,25 @@ class UpdateGraph(object):
         """The 6-tuple of ``ppo_update`` from a graph replay, or None: the caller runs the eager update."""
         if not self._trainer_ok():
             return None
+        sample = Minibatch(*sample)     # (named, not converted: a replay only copies device tensors)
         sig, rows = self._signature(sample, update_actor)
         if sig is None:
             return None
         e = self.entries.get(sig)
         if e is None:       # first sight of this signature: the eager update is the warm-up
-            self._remember(sig, {"state": "warm"})
+            self._remember(sig, _Entry())
             self.warmups += 1
             return None
-        if e["state"] == "failed":
+        if e.state == "failed":
             return None
         self.order.remove(sig)
         self.order.append(sig)
         t = self.t
-        scales = t.dp.minibatch_scales(sample[8], sample[6], t._use_policy_active_masks, t._use_value_active_masks)
+        scales = t.dp.minibatch_scales(sample.active_masks, sample.returns, t._use_policy_active_masks,
+                                       t._use_value_active_masks)
         if scales is None:
             return None
-        if e["state"] == "warm":
+        if e.state == "warm":
             if self.captures >= self.MAX_CAPTURES_WITHOUT_PAYOFF and self.replays < 4 * self.captures:
                 # the signatures keep changing (addresses of the matrices the minibatches point into that do not survive a
                 # train(), ...): captures cost ~100 ms each and are not paying for themselves -- stay eager from here on
@@ -165,8 +191,7 @@ class UpdateGraph(object):
             except Exception as exc:
                 # Nothing of this minibatch has executed (a capture only records; _capture itself deals with a failure AFTER the
                 # front half ran): whatever the capture cannot take stays eager, loudly.
-                e.clear()
-                e["state"] = "failed"
+                e.fail()
                 self.capture_failures += 1
                 print("update graph: capture failed (%s: %s); this update shape stays eager" % (type(exc).__name__, exc))
                 torch.cuda.synchronize(t.device)
@@ -205,15 +230,15 @@ class UpdateGraph(object):
                 static.append(x.clone())
             else:
                 static.append(x)            # None, or a view that is read in place (see _signature)
-        e["static"] = tuple(static)
-        e["inputs"] = self._tensors(static)
+        e.static = Minibatch(*static)
+        e.inputs = self._tensors(static)
         cur = self._tensors(sample)             # the static inputs start out as copies of this minibatch
-        e["loaded"] = ([(id(x), x._version) for x in cur], cur)
-        e["scales"] = scales.clone()
-        e["scales_src"] = scales
+        e.loaded = ([(id(x), x._version) for x in cur], cur)
+        e.scales = scales.clone()
+        e.scales_src = scales
         opts = (t.policy.actor_optimizer, t.policy.critic_optimizer)
-        e["lr"] = [torch.full((1,), float(o.param_groups[0]["lr"]), dtype=torch.float64, device=dev) for o in opts]
-        e["lr_val"] = [float(o.param_groups[0]["lr"]) for o in opts]
+        e.lr = [torch.full((1,), float(o.param_groups[0]["lr"]), dtype=torch.float64, device=dev) for o in opts]
+        e.lr_val = [float(o.param_groups[0]["lr"]) for o in opts]
         params = [p for net in (t.policy.actor, t.policy.critic) for p in net.parameters() if p.requires_grad]
         if self.pool is None:
             self.pool = torch.cuda.graph_pool_handle()
@@ -221,15 +246,14 @@ class UpdateGraph(object):
         # (thread_local: the capture must not outlaw what OTHER threads do meanwhile -- RCCL's watchdog polls the events of
         # earlier collectives -- while the autograd thread's launches into the capturing stream are recorded all the same)
         with capturing(front, pool=self.pool, capture_error_mode="thread_local"):
-            value_loss, policy_loss, dist_entropy, ratio = t.ppo_update(e["static"], update_actor, _front_only=True,
-                                                                        _scales=e["scales"])
+            value_loss, policy_loss, dist_entropy, ratio = t.ppo_update(e.static, update_actor, _front_only=True,
+                                                                        _scales=e.scales)
             if not t.dp.active:
-                norms = t._update_back(update_actor, lr_devices=e["lr"])
-        e["front"] = front
-        e["back"] = None
+                norms = t._update_back(update_actor, lr_devices=e.lr)
+        e.front = front
         if t.dp.active:
             # the gradient exchange stays eager between the two halves (one batched copy + ONE collective, utils/dist.py)
-            e["front_grads"] = [p.grad for p in t.dp._params]
+            e.front_grads = [p.grad for p in t.dp._params]
             front.replay()                      # (a capture executes nothing: run the front once so that the bucket is real)
             t.dp.all_reduce_grads()             # -> every param.grad is a view of the reduced flat bucket
             # From here on this minibatch HAS been evaluated: ValueNorm fed, gradients reduced, one collective issued on
@@ -240,22 +264,21 @@ class UpdateGraph(object):
                 with capturing(back, pool=self.pool, capture_error_mode="thread_local"):
                     if os.environ.get("MAPPO_TEST_FAIL_BACK_CAPTURE", "0") == "1":     # (tests/test_gpu_update_graph.py)
                         raise RuntimeError("forced by MAPPO_TEST_FAIL_BACK_CAPTURE")
-                    norms = t._update_back(update_actor, lr_devices=e["lr"])
+                    norms = t._update_back(update_actor, lr_devices=e.lr)
             except Exception as exc:
                 torch.cuda.synchronize(dev)
                 print("update graph: capture of the optimiser half failed after the front half ran (%s: %s); this update "
                       "is finished eagerly, the shape stays eager" % (type(exc).__name__, exc))
                 norms = t._update_back(update_actor)
                 out = tuple(x.detach().clone() for x in (value_loss, norms[1], policy_loss, dist_entropy, norms[0], ratio))
-                e.clear()
-                e["state"] = "failed"
+                e.fail()
                 self.capture_failures += 1
                 return out
-            e["back"] = back
-            e["front_done"] = True              # the front already ran for the minibatch that triggered the capture
-        e["grads"] = [(p, p.grad) for p in params]
-        e["out"] = (value_loss, norms[1], policy_loss, dist_entropy, norms[0], ratio)
-        e["state"] = "ready"
+            e.back = back
+            e.front_done = True
+        e.grads = [(p, p.grad) for p in params]
+        e.out = (value_loss, norms[1], policy_loss, dist_entropy, norms[0], ratio)
+        e.state = "ready"
         self.captures += 1
         self._state = self._state_key()
         return None
@@ -264,28 +287,29 @@ class UpdateGraph(object):
         t = self.t
         for i, o in enumerate((t.policy.actor_optimizer, t.policy.critic_optimizer)):
             lr = float(o.param_groups[0]["lr"])
-            if lr != e["lr_val"][i]:
-                e["lr"][i].fill_(lr)
-                e["lr_val"][i] = lr
-        if e.pop("front_done", False):
+            if lr != e.lr_val[i]:
+                e.lr[i].fill_(lr)
+                e.lr_val[i] = lr
+        if e.front_done:
             # (multi-GPU capture: the front and the gradient exchange already ran for this very minibatch)
-            e["back"].replay()
+            e.front_done = False
+            e.back.replay()
         else:
             # inputs: one batched copy, skipped when this very minibatch (same tensor objects, unchanged) is already loaded --
             # the whole-batch tuple of a one-minibatch epoch is handed out again in every epoch
             cur = self._tensors(sample)
             key = [(id(x), x._version) for x in cur]
-            if e["loaded"] is None or e["loaded"][0] != key:
-                torch._foreach_copy_(e["inputs"], cur)
-                e["loaded"] = (key, cur)        # (holding the sources keeps their ids from being recycled)
-            if e["scales_src"] is not scales:
-                e["scales"].copy_(scales)
-                e["scales_src"] = scales
-            e["front"].replay()
-            if e["back"] is not None:
-                t.dp.all_reduce_from(e["front_grads"])
-                e["back"].replay()
-        for p, g in e["grads"]:                 # what a caller finds in .grad after an update (clipped, reduced)
+            if e.loaded is None or e.loaded[0] != key:
+                torch._foreach_copy_(e.inputs, cur)
+                e.loaded = (key, cur)           # (holding the sources keeps their ids from being recycled)
+            if e.scales_src is not scales:
+                e.scales.copy_(scales)
+                e.scales_src = scales
+            e.front.replay()
+            if e.back is not None:
+                t.dp.all_reduce_from(e.front_grads)
+                e.back.replay()
+        for p, g in e.grads:                    # what a caller finds in .grad after an update (clipped, reduced)
             p.grad = g
         self.replays += 1
-        return e["out"]
+        return e.out

@@ -121,21 +121,7 @@ class DataParallel(object):
         those)."""
         if not self.active:
             return
-        pieces = []
-        off = 0
-        for p in self._params:
-            n = p.numel()
-            pieces.append(self._zeros[off:off + n] if p.grad is None else p.grad.reshape(-1))
-            off += n
-        torch.cat(pieces, out=self._flat)
-        timed = self._timing is not None and self._flat.is_cuda
-        if timed:
-            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            ev[0].record()
-        dist.all_reduce(self._flat, op=dist.ReduceOp.SUM, group=self.group)
-        if timed:
-            ev[1].record()
-            self._timing.append(ev)
+        self.all_reduce_from([p.grad for p in self._params])
         off = 0
         for p in self._params:
             n = p.numel()
@@ -173,19 +159,6 @@ class DataParallel(object):
         ev = self._timing or []
         ms = sum(a.elapsed_time(b) for a, b in ev)
         return len(ev), ms, (0 if self._flat is None else self._flat.numel() * 4)
-
-    def loss_weights(self, active_masks, policy_masked, value_masked):
-        """(w_actor, w_critic): local / global denominators of the masked means
-        (reference r_mappo.py:135-139, 84-87)."""
-        if not self.active:
-            return 1.0, 1.0
-        local = torch.stack([active_masks.detach().sum().double(),
-                             torch.full((), float(active_masks.shape[0]), dtype=torch.float64,
-                                        device=active_masks.device)])
-        total = local.clone()
-        self.all_reduce(total)
-        w = (local / total).float()
-        return (w[0] if policy_masked else w[1]), (w[0] if value_masked else w[1])
 
     def minibatch_stats(self, active_masks, return_batch, policy_masked, value_masked):
         """ONE collective for everything a minibatch needs globally before its loss is formed:

@@ -109,6 +109,57 @@ def test_trainer_fused_equals_unfused(monkeypatch, recurrent):
     assert torch.allclose(n1, n0, rtol=1e-6, atol=1e-10)
 
 
+@pytest.mark.parametrize("cname", ["mlp", "gru"])
+def test_row_span_microbatching_is_equivalent_on_device(gold, cname):
+    """The device twin of tests/test_networks_trainer_cpu.py::test_row_span_microbatching_is_equivalent: the fused loss (K7)
+    evaluated in several row spans -- rows for the feed-forward case, whole chunks for the recurrent one -- accumulates
+    gradients and the four sums into the same update as one pass, to the CPU test's own tolerances.  Several spans stay
+    eager: nothing of such a minibatch is replayed from a graph."""
+    from onpolicy.algorithms.r_mappo.algorithm.rMAPPOPolicy import R_MAPPOPolicy
+    from onpolicy.algorithms.r_mappo.r_mappo import R_MAPPO
+    from onpolicy.utils.shared_buffer import SharedReplayBuffer
+    z = gold.npz("trainer_cases")
+    key = "trn_%s_" % cname
+    spec = gold.meta("trainer_cases")[cname]["spec"]
+    # 200 elements / 11 features -> at most 18 rows (3 chunks of 5 steps) per span, 60 rows (12 chunks) per minibatch
+    rows = spec["T"] * spec["N"] * spec["A"] // spec["args"]["num_mini_batch"]
+    per_span = 200 // max(spec["Do"], spec["Ds"])
+    if cname == "gru":
+        per_span = per_span // spec["args"]["data_chunk_length"] * spec["args"]["data_chunk_length"]
+    assert -(-rows // per_span) >= 3
+    results = []
+    for cap in (1 << 30, 200):
+        args = make_args(episode_length=spec["T"], n_rollout_threads=spec["N"], sampler_rng="host", **spec["args"])
+        spaces = Box((spec["Do"],)), Box((spec["Ds"],)), Discrete(spec["na"])
+        torch.manual_seed(1)
+        np.random.seed(1)
+        policy = R_MAPPOPolicy(args, *spaces, device=DEV)
+        trainer = R_MAPPO(args, policy, device=DEV)
+        assert trainer._fused_loss
+        trainer.MAX_TENSOR_ELEMENTS = cap
+        buf = SharedReplayBuffer(args, spec["A"], *spaces, device=DEV)
+        for name in ("share_obs", "obs", "rnn_states", "rnn_states_critic", "actions", "value_preds", "masks",
+                     "bad_masks", "active_masks", "action_log_probs", "available_actions", "rewards"):
+            dst = getattr(buf, name)
+            if dst.stride()[0] != 0:
+                dst.copy_(torch.from_numpy(z[key + "buf_" + name]))
+        buf.compute_returns(z[key + "next_value"], trainer.value_normalizer)
+        trainer.prep_training()
+        torch.manual_seed(21)
+        info = trainer.train(buf)
+        if cap == 200:
+            assert trainer._update_graph.replays == 0
+        results.append((info, {k: v.cpu() for k, v in policy.actor.state_dict().items()},
+                        {k: v.cpu() for k, v in policy.critic.state_dict().items()}))
+    (i0, a0, c0), (i1, a1, c1) = results
+    for k in i0:
+        print("row spans on device %s %s: %.9g one pass, %.9g in spans" % (cname, k, i0[k], i1[k]))
+        assert i1[k] == pytest.approx(i0[k], rel=1e-4, abs=1e-6), k
+    for sd0, sd1 in ((a0, a1), (c0, c1)):
+        for k in sd0:
+            np.testing.assert_allclose(sd1[k].numpy(), sd0[k].numpy(), rtol=1e-4, atol=1e-5, err_msg=k)
+
+
 @pytest.mark.parametrize("na,with_avail", [(5, False), (5, True), (18, True), (48, True), (1, False)])
 def test_categorical_sample_kernel_vs_the_framework_rule(na, with_avail):
     """K14 (``mappo_categorical_sample``): masking + one draw per row + its log-probability in one launch, against the
