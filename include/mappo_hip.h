@@ -146,18 +146,21 @@ int mappo_advantages_f32(const float* returns, const float* value_preds, const f
                          const float* active_masks, float* advantages, double* adv_partials,
                          int T, int64_t C, mappo_stream_t stream);
 
-/* Tuning hook for benchmarks: selects the kernel variant used by mappo_gae_f32
- * (0 = automatic). All variants produce bit-identical results. Returns the previous
- * value. */
+/* Tuning hook for benchmarks: selects the kernel used by mappo_gae_f32 (0 = automatic).  variant % 1000 names the kernel:
+ * 36, 54, 56, 57 = the four LDS-DMA ring shapes the automatic choice picks from, 70 = the time-parallel scan (71 and 72,
+ * scan widths that are no longer built, are aliases of 70), 99 = one lane per column.  Any other number has no kernel
+ * of its own and runs the one-lane-per-column kernel.  variant / 1000 carries option bits for the ring kernels:
+ * 1 = XCD-contiguous strip order, 2 = non-temporal DMA loads (the automatic choice sets both).  All of them but the scan
+ * produce bit-identical results.  Returns the previous value. */
 int mappo_gae_set_variant(int variant);
 
 /* The variant the most recent mappo_gae_f32 call of this process launched (0 before the first call):
- * 70-72 = the time-parallel scan (tolerance mode), 99 = one lane per column, the others the bit-exact
- * strip kernels.  For tests that must know which arithmetic a shape took. */
+ * 70 = the time-parallel scan (tolerance mode), 99 = one lane per column, 36 / 54 / 56 / 57 the bit-exact
+ * LDS-DMA ring kernels (a number without a kernel of its own is reported as given and ran one lane per column).  For tests that must know which arithmetic a shape took. */
 int mappo_gae_last_variant(void);
 
 /* Measurement hook for benchmarks: mappo_gae_time_next_launch arms one of 64 slots (returned, >= 0; they are reused in a ring)
- * and the NEXT strip / LDS-DMA launch of mappo_gae_f32 in this process (every GAE-mode call with aligned columns; not the
+ * and the NEXT LDS-DMA ring launch of mappo_gae_f32 in this process (every GAE-mode call with aligned columns; not the
  * one-lane-per-column kernel, not the scan) is bracketed by that slot's HIP event pair at dispatch level
  * (hipExtLaunchKernelGGL: kernel begin / end timestamps, what rocprofv3 --kernel-trace reports), on the stream of that call.
  * mappo_gae_timed_launch_ms(slot) waits for that launch and returns its duration in milliseconds; MAPPO_E_FLAGS if the slot

@@ -11,17 +11,26 @@
 //
 // The scan is HBM-bound (16..24 B per (t, column) element, ~6 flops), and at the
 // north-star size there are only C = 32768 columns = 512 wavefronts for 256 CUs, so
-// bandwidth comes from memory-level parallelism per wave, not from occupancy:
-//   * "strip" kernels: a workgroup owns a strip of W columns; all its lanes stream
-//     [TC rows x W cols] tiles of every input field with 16-byte loads into registers
-//     (the prefetch stage), drop them into LDS (the transpose stage: load lanes are
-//     (row, 4-col group), compute lanes are columns), and one wave walks the tile
-//     backwards in time out of LDS while the next tile's loads are in flight.
-//   * "column" kernel: one lane per column with plain 4-byte loads; used for any C / any
-//     alignment and for the non-GAE modes.
+// bandwidth comes from memory-level parallelism per wave, not from occupancy.  The kernels:
+//   * gae_dma_epi_kernel (variants 57, 54, 56: the automatic choice from 8192 columns up): a
+//     workgroup owns a strip of W columns; producer waves stream [TC rows x W cols] tiles of
+//     every input field straight into an LDS ring with 128-bit LDS-DMA loads, one walker wave
+//     per 64 columns walks each tile backwards in time out of LDS, and the producers run the
+//     epilogue (returns / advantages / moments) one tile behind the walker.
+//   * gae_dma_kernel (variant 36, narrower buffers): the same ring; the walker stores its own
+//     results.
+//   * gae_scan_kernel (variant 70): time-parallel scan for narrow buffers, tolerance mode.
+//   * gae_column_kernel (variant 99 and every number without a kernel of its own): one lane per
+//     column with plain 4-byte loads; any C, any alignment, and the non-GAE modes.
+//   * gae_mat_kernel (the multi-agent-transformer branches) and the advantage / moment kernels
+//     (K5) behind their own entry points.
+// The shapes that tuning tried and dropped (cooperative strips, a register-prefetch pipe, other
+// ring shapes and depths, a 16-column scan) are no longer built; their A/B records remain under
+// profiles/.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "mappo_hip.h"
 #include "mappo_internal.h"
@@ -87,6 +96,32 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// One row of the partials array: the wave's three moments, written by its lane 0.
+__device__ __forceinline__ void write_partials(const GaeArgs& a, long long row, int lane, double s1, double s2,
+                                               double cnt) {
+    if (a.partials != nullptr) {
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
+        cnt = wave_sum(cnt);
+        if (lane == 0) {
+            double* p = a.partials + row * 3;
+            p[0] = s1;
+            p[1] = s2;
+            p[2] = cnt;
+        }
+    }
+}
+
+// D(v) = v * sigma + mu of the value normaliser (valuenorm.py:75); the identity without one.
+__device__ __forceinline__ void load_denorm(const GaeArgs& a, bool denorm, float& sigma, float& mu) {
+    sigma = 1.f;
+    mu = 0.f;
+    if (denorm) {
+        sigma = a.denorm[0];
+        mu = a.denorm[1];
+    }
+}
+
 
 // Rows of the partials array that no workgroup owns are zeroed by workgroup 0, so that the
 // fixed-size reduction needs no separate memset launch.
@@ -100,53 +135,10 @@ __device__ __forceinline__ void zero_unowned_partials(double* partials, long lon
     }
 }
 
-// ------------------------------------------------------------------ strip kernels ----
-// Shared pieces of the two strip kernels.  A tile is TC consecutive time steps of one strip
-// of W columns; in LDS it is [slot][TC][W] floats with slots r, v, m, [bad], [active].
+// ------------------------------------------------------------------ ring kernels ----
+// A tile is TC consecutive time steps of one strip of W columns; in LDS it is [slot][TC][W] floats
+// with slots r, v, m, [bad], [active].
 //
-// Loads are branch-free: out-of-range rows / columns / surplus lanes are CLAMPED to a valid
-// address instead of predicated, so that every tile issues the same straight-line sequence of
-// global_load_dwordx4 and the compiler can wait for the oldest tile with a counted
-// s_waitcnt vmcnt(N) while younger tiles stay in flight (a predicated load makes it fall back
-// to vmcnt(0), which drains the whole prefetch queue).
-// Implemented as macros over local arrays with literal indices: anything the compiler cannot
-// fully scalarise (arrays passed by reference, runtime buffer indices) lands in scratch memory.
-#define MAPPO_TILE_CONSTS(W_, TC_, NL_, PTL_, ACT_)                                              \
-    constexpr int V = (W_) / 4;                    /* float4 per tile row */                     \
-    constexpr int NVEC = (TC_) * V;                /* float4 per field per tile */               \
-    constexpr int PER = (NVEC + (NL_) - 1) / (NL_);/* float4 per loader thread per field */      \
-    constexpr int NF = 3 + ((PTL_) ? 1 : 0) + ((ACT_) ? 1 : 0);                                  \
-    constexpr int NLOAD = (NL_);
-
-// slot s -> field base pointer (masks / bad_masks are read at row t+1)
-#define MAPPO_SLOT_BASE(s)                                                                       \
-    ((s) == 0 ? a.rewards : (s) == 1 ? (const float*)a.value_preds : (s) == 2 ? a.masks + a.C    \
-     : ((s) == 3 && PTL) ? a.bad + a.C : a.active)
-
-#define MAPPO_LOAD_TILE(PRE, LTID, TBASE)                                                        \
-    _Pragma("unroll") for (int s_ = 0; s_ < NF; ++s_) {                                          \
-        const float* fb_ = MAPPO_SLOT_BASE(s_);                                                  \
-        _Pragma("unroll") for (int p_ = 0; p_ < PER; ++p_) {                                     \
-            int i_ = (LTID) + p_ * NLOAD;                                                        \
-            if (i_ > NVEC - 1) i_ = NVEC - 1;                                                    \
-            int row_ = i_ / V;                                                                   \
-            int c4_ = i_ - row_ * V;                                                             \
-            int t_ = (TBASE) + row_;                                                             \
-            if (t_ < 0) t_ = 0;                                                                  \
-            long long lc_ = col0 + c4_ * 4;                                                      \
-            if (lc_ > a.C - 4) lc_ = a.C - 4;                                                    \
-            PRE[s_][p_] = *reinterpret_cast<const vf4*>(fb_ + (long long)t_ * a.C + lc_);     \
-        }                                                                                        \
-    }
-
-#define MAPPO_STASH_TILE(PRE, LTID, LDS4)                                                        \
-    _Pragma("unroll") for (int s_ = 0; s_ < NF; ++s_) {                                          \
-        _Pragma("unroll") for (int p_ = 0; p_ < PER; ++p_) {                                     \
-            int i_ = (LTID) + p_ * NLOAD;                                                        \
-            if ((NVEC % NLOAD == 0) || i_ < NVEC) (LDS4)[s_ * NVEC + i_] = PRE[s_][p_];          \
-        }                                                                                        \
-    }
-
 // Walk one tile backwards in time out of LDS (one lane per column).  The walker wave is the serial
 // part of the kernel (400 dependent steps), so its instruction stream is kept lean:
 //   * the LDS operands of U consecutive steps are fetched in one batch before they are needed (they
@@ -161,7 +153,6 @@ __device__ __forceinline__ void walk_tile_impl(const GaeArgs& a, const float* ld
     constexpr int U = TC % 8 == 0 ? 8 : (TC % 4 == 0 ? 4 : (TC % 2 == 0 ? 2 : 1));
     static_assert(TC % U == 0, "tile length vs walker batch");
     if (!live) return;
-    constexpr bool has_adv = ADV;
     // LDS column of this lane: its lane for strips up to one wave wide, or the caller's column for
     // strips shared by several walker waves
     const int lc = lds_col >= 0 ? lds_col : lane;
@@ -174,7 +165,7 @@ __device__ __forceinline__ void walk_tile_impl(const GaeArgs& a, const float* ld
     const float gamma = a.gamma, gl = a.gl;
     const long long C = a.C;
     float* pret = a.returns + (long long)(tbase + TC - 1) * C + col;
-    float* padv = has_adv ? a.adv + (long long)(tbase + TC - 1) * C + col : nullptr;
+    float* padv = ADV ? a.adv + (long long)(tbase + TC - 1) * C + col : nullptr;
     for (int s0 = TC - 1; s0 >= slo; s0 -= U) {
         float r[U], v0[U], m1[U], b1[U], am[U];
 #pragma unroll
@@ -194,7 +185,7 @@ __device__ __forceinline__ void walk_tile_impl(const GaeArgs& a, const float* ld
                 float ret = gae_step<PTL, DENORM>(r[u], v0[u], m1[u], b1[u], sigma, mu, gamma, gl, dv1, g, dv0);
                 *pret = ret;
                 pret -= C;
-                if (has_adv) {
+                if (ADV) {
                     float adv = ret - dv0;             // r_mappo.py:180 (from the rounded return)
                     *padv = adv;
                     padv -= C;
@@ -210,7 +201,7 @@ __device__ __forceinline__ void walk_tile_impl(const GaeArgs& a, const float* ld
                 float ret = gae_step<PTL, DENORM>(r[u], v0[u], m1[u], b1[u], sigma, mu, gamma, gl, dv1, g, dv0);
                 *pret = ret;
                 pret -= C;
-                if (has_adv) {
+                if (ADV) {
                     float adv = ret - dv0;
                     *padv = adv;
                     padv -= C;
@@ -236,15 +227,11 @@ __device__ __forceinline__ void walk_tile(const GaeArgs& a, const float* ldsf, i
                                                        s2, cnt, lds_col);
 }
 
-__device__ __forceinline__ void walker_prologue(const GaeArgs& a, bool live, long long col, bool denorm,
-                                                float& sigma, float& mu, float& dv1) {
-    sigma = 1.f;
-    mu = 0.f;
-    if (denorm) {
-        sigma = a.denorm[0];
-        mu = a.denorm[1];
-    }
-    dv1 = 0.f;
+// The walker's start: the bootstrap value goes into row T of value_preds, D() of it is the first
+// step's dv1.
+__device__ __forceinline__ float walker_prologue(const GaeArgs& a, bool live, long long col, bool denorm,
+                                                 float sigma, float mu) {
+    float dv1 = 0.f;
     if (live) {
         float nv = a.next_value[col];
         a.value_preds[(long long)a.T * a.C + col] = nv;  // shared_buffer.py:187,218
@@ -254,82 +241,7 @@ __device__ __forceinline__ void walker_prologue(const GaeArgs& a, bool live, lon
             dv1 = s + mu;
         }
     }
-}
-
-__device__ __forceinline__ void walker_epilogue(const GaeArgs& a, int lane, double s1, double s2, double cnt) {
-    if (a.partials != nullptr) {
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        cnt = wave_sum(cnt);
-        if (lane == 0) {
-            double* p = a.partials + (long long)blockIdx.x * 3;
-            p[0] = s1;
-            p[1] = s2;
-            p[2] = cnt;
-        }
-    }
-}
-
-// ---- "pipe" kernel: one walker wave + NPROD producer waves per strip ---------------------
-// Producers keep NBUF tiles in flight in registers (global -> VGPR), drop the oldest into
-// one half of a double-buffered LDS tile while the walker consumes the other half, and meet
-// the walker at ONE barrier per tile.  The walker does nothing but the recurrence.
-template <int W, int NPROD, int TC, int NBUF, bool PTL, bool DENORM, bool ACT>
-__global__ void __launch_bounds__((NPROD + 1) * 64) gae_pipe_kernel(GaeArgs a) {
-    MAPPO_TILE_CONSTS(W, TC, NPROD * 64, PTL, ACT)
-    static_assert(NBUF >= 1 && NBUF <= 4, "prefetch depth");
-    constexpr int TILE4 = NF * NVEC;             // float4 per LDS tile buffer
-    extern __shared__ vf4 lds4[];             // [2][NF][TC][V]
-    const int T = a.T;
-    const int nch = (T + TC - 1) / TC;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const long long col0 = (long long)blockIdx.x * W;
-    zero_unowned_partials(a.partials, a.partial_rows);
-
-    if (wave == 0) {
-        const int lane = threadIdx.x;
-        const long long col = col0 + lane;
-        const bool live = lane < W && col < a.C;
-        float sigma, mu, dv1, g = 0.f;
-        double s1 = 0.0, s2 = 0.0, cnt = 0.0;
-        walker_prologue(a, live, col, DENORM, sigma, mu, dv1);
-        __syncthreads();                                        // tile 0 is in LDS half 0
-        for (int k = 0; k < nch; ++k) {
-            const float* tile = reinterpret_cast<const float*>(lds4 + (k & 1) * TILE4);
-            walk_tile<W, TC, PTL, DENORM, ACT>(a, tile, lane, col, live, T - (k + 1) * TC, sigma, mu, g,
-                                               dv1, s1, s2, cnt);
-            __syncthreads();                                    // tile k+1 stashed, tile k released
-        }
-        walker_epilogue(a, lane, s1, s2, cnt);
-    } else {
-        const int ltid = threadIdx.x - 64;
-        // tile m lives in register buffer m % NBUF
-        vf4 pre0[NF][PER], pre1[NF][PER], pre2[NF][PER], pre3[NF][PER];
-        MAPPO_LOAD_TILE(pre0, ltid, T - 1 * TC)
-        if (NBUF > 1) { MAPPO_LOAD_TILE(pre1, ltid, T - 2 * TC) }
-        if (NBUF > 2) { MAPPO_LOAD_TILE(pre2, ltid, T - 3 * TC) }
-        if (NBUF > 3) { MAPPO_LOAD_TILE(pre3, ltid, T - 4 * TC) }
-        MAPPO_STASH_TILE(pre0, ltid, lds4)
-        MAPPO_LOAD_TILE(pre0, ltid, T - (NBUF + 1) * TC)
-        __syncthreads();
-        // step k: the walker walks tile k; producers stash tile k+1 into LDS half (k+1)&1 and
-        // refill its register buffer with tile k+1+NBUF
-#define MAPPO_PIPE_STEP(PRE)                                                                     \
-        if (k < nch) {                                                                           \
-            MAPPO_STASH_TILE(PRE, ltid, lds4 + ((k + 1) & 1) * TILE4)                            \
-            MAPPO_LOAD_TILE(PRE, ltid, T - (k + 2 + NBUF) * TC)                                  \
-            __syncthreads();                                                                     \
-        }                                                                                        \
-        ++k;
-        for (int k = 0; k < nch;) {
-            if (NBUF == 1) { MAPPO_PIPE_STEP(pre0) }
-            if (NBUF == 2) { MAPPO_PIPE_STEP(pre1) MAPPO_PIPE_STEP(pre0) }
-            if (NBUF == 3) { MAPPO_PIPE_STEP(pre1) MAPPO_PIPE_STEP(pre2) MAPPO_PIPE_STEP(pre0) }
-            if (NBUF == 4) { MAPPO_PIPE_STEP(pre1) MAPPO_PIPE_STEP(pre2) MAPPO_PIPE_STEP(pre3) MAPPO_PIPE_STEP(pre0) }
-        }
-#undef MAPPO_PIPE_STEP
-        (void)pre1; (void)pre2; (void)pre3;
-    }
+    return dv1;
 }
 
 // ---- "dma" kernel: producers stream tiles straight into an LDS ring with LDS-DMA ---------
@@ -384,17 +296,66 @@ __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// The producers' DMA issue path of both ring kernels.  Loads are branch-free: out-of-range rows /
+// columns are CLAMPED to a valid address instead of predicated, so that every tile is the same
+// straight-line sequence of LPT instructions per producer wave and the counted waits below hold.
+template <int W, int TC, int NPROD, int NF, bool PTL>
+struct TileDma {
+    static constexpr int RPI = 256 / W;            // tile rows per wave instruction
+    static constexpr int IPS = TC / RPI;           // instructions per slot (field) per tile
+    static constexpr int LPT = NF * IPS / NPROD;   // instructions per producer wave per tile
+    static constexpr int TILE_FLOATS = NF * TC * W;
+    static_assert(W <= 256 && (W <= 64 || W % 64 == 0), "strip width");
+    static_assert(TC % RPI == 0 && IPS % NPROD == 0, "row groups must split evenly over the producers");
+
+    const float *fb0, *fb1, *fb2, *fb3, *fb4;      // field bases at this lane's (clamped) column
+    long long C;
+    unsigned lds_base;                             // LDS byte address of the ring
+    int pw, r0;                                    // producer index; this lane's row (of RPI) inside one instruction
+    bool nt;
+
+    __device__ __forceinline__ TileDma(const GaeArgs& a, long long col0, const float* ring, int pw_, int lane)
+        : C(a.C), lds_base((unsigned)(uintptr_t)ring), pw(pw_), nt((a.opts & 2) != 0) {
+        const int row = lane / (W / 4);
+        const int c4 = lane - row * (W / 4);       // this lane's 4-column group
+        r0 = row;
+        long long lc = col0 + c4 * 4;
+        if (lc > C - 4) lc = C - 4;                // clamp instead of predicating
+        fb0 = a.rewards + lc;
+        fb1 = a.value_preds + lc;
+        fb2 = a.masks + C + lc;                    // masks / bad_masks are read at row t+1
+        fb3 = (PTL ? a.bad + C : a.active) + lc;
+        fb4 = a.active + lc;
+    }
+
+    // tile with time base `tbase` -> ring slot `slot`; field index is compile-time, this wave
+    // takes row groups pw, pw + NPROD, ... of every field
+    __device__ __forceinline__ void issue_tile(int tbase, int slot) const {
+        const unsigned slot_addr = lds_base + (unsigned)slot * (TILE_FLOATS * 4);
+#pragma unroll
+        for (int s = 0; s < NF; ++s) {
+            const float* fbs = s == 0 ? fb0 : s == 1 ? fb1 : s == 2 ? fb2 : (s == 3 && PTL) ? fb3 : fb4;
+#pragma unroll
+            for (int q = 0; q < IPS / NPROD; ++q) {
+                const int rg = pw + q * NPROD;     // row group inside the tile
+                int t = tbase + rg * RPI + r0;
+                if (t < 0) t = 0;
+                const float* src = fbs + (long long)t * C;
+                const unsigned dst = slot_addr + (unsigned)((s * TC + rg * RPI) * W * 4);
+                if (nt) lds_dma_16B<true>(src, dst);
+                else lds_dma_16B<false>(src, dst);
+            }
+        }
+    }
+};
+
 template <int W, int NPROD, int TC, int R, bool PTL, bool DENORM, bool ACT>
 __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_kernel(GaeArgs a) {
     constexpr int NWALK = (W + 63) / 64;           // walker waves (64 columns each)
     constexpr int NF = 3 + (PTL ? 1 : 0) + (ACT ? 1 : 0);
-    constexpr int RPI = 256 / W;                   // tile rows per wave instruction
-    constexpr int IPS = TC / RPI;                  // instructions per slot (field) per tile
-    constexpr int IPT = NF * IPS;                  // instructions per tile
-    constexpr int LPT = IPT / NPROD;               // instructions per producer wave per tile
-    constexpr int TILE_FLOATS = NF * TC * W;
-    static_assert(W <= 256 && (W <= 64 || W % 64 == 0), "strip width");
-    static_assert(TC % RPI == 0 && IPS % NPROD == 0, "row groups must split evenly over the producers");
+    using Dma = TileDma<W, TC, NPROD, NF, PTL>;
+    constexpr int LPT = Dma::LPT;
+    constexpr int TILE_FLOATS = Dma::TILE_FLOATS;
     static_assert(R >= 2 && (R - 2) * LPT < 64, "ring depth vs the 6-bit vmcnt");
     static_assert(R * TILE_FLOATS * 4 <= 160 * 1024, "LDS ring");
 
@@ -404,7 +365,6 @@ __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_kernel(G
     const int nch = (T + TC - 1) / TC;
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const long long col0 = (long long)strip_of_block(a) * W;
-    const bool nt = (a.opts & 2) != 0;
     zero_unowned_partials(a.partials, a.partial_rows, NWALK);
 
     if (wave < NWALK) {
@@ -412,9 +372,10 @@ __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_kernel(G
         const int lds_col = NWALK > 1 ? wave * 64 + lane : -1;
         const long long col = col0 + (NWALK > 1 ? wave * 64 : 0) + lane;
         const bool live = (NWALK > 1 || lane < W) && col < a.C;
-        float sigma, mu, dv1, g = 0.f;
+        float sigma, mu, g = 0.f;
         double s1 = 0.0, s2 = 0.0, cnt = 0.0;
-        walker_prologue(a, live, col, DENORM, sigma, mu, dv1);
+        load_denorm(a, DENORM, sigma, mu);
+        float dv1 = walker_prologue(a, live, col, DENORM, sigma, mu);
         __syncthreads();                                        // tile 0 landed
         int slot = 0;
         for (int k = 0; k < nch; ++k) {
@@ -423,60 +384,17 @@ __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_kernel(G
             slot = slot + 1 == R ? 0 : slot + 1;
             __syncthreads();                                    // tile k+1 landed, tile k released
         }
-        if (a.partials != nullptr) {
-            s1 = wave_sum(s1);
-            s2 = wave_sum(s2);
-            cnt = wave_sum(cnt);
-            if (lane == 0) {
-                double* p = a.partials + ((long long)blockIdx.x * NWALK + wave) * 3;
-                p[0] = s1;
-                p[1] = s2;
-                p[2] = cnt;
-            }
-        }
+        write_partials(a, (long long)blockIdx.x * NWALK + wave, lane, s1, s2, cnt);
     } else {
-        const int lane = threadIdx.x & 63;
-        const int pw = wave - NWALK;                            // producer index
-        const unsigned lds_base = (unsigned)(uintptr_t)ldsf;    // LDS byte address of the ring
-        // this lane's place inside one instruction: row r0 (of RPI), 4-column group c4
-        const int r0 = lane / (W / 4);
-        const int c4 = lane - r0 * (W / 4);
-        long long lc = col0 + c4 * 4;
-        if (lc > a.C - 4) lc = a.C - 4;                         // clamp instead of predicating
-        const float* fb0 = a.rewards + lc;
-        const float* fb1 = a.value_preds + lc;
-        const float* fb2 = a.masks + a.C + lc;
-        const float* fb3 = (PTL ? a.bad + a.C : a.active) + lc;
-        const float* fb4 = a.active + lc;
-
-        // tile with time base `tbase` -> ring slot `slot`; field index is compile-time, this
-        // wave takes row groups pw, pw + NPROD, ... of every field
-        auto issue_tile = [&](int tbase, int slot) {
-            const unsigned slot_addr = lds_base + (unsigned)slot * (TILE_FLOATS * 4);
-#pragma unroll
-            for (int s = 0; s < NF; ++s) {
-                const float* fbs = s == 0 ? fb0 : s == 1 ? fb1 : s == 2 ? fb2 : (s == 3 && PTL) ? fb3 : fb4;
-#pragma unroll
-                for (int q = 0; q < IPS / NPROD; ++q) {
-                    const int rg = pw + q * NPROD;              // row group inside the tile
-                    int t = tbase + rg * RPI + r0;
-                    if (t < 0) t = 0;
-                    const float* src = fbs + (long long)t * a.C;
-                    const unsigned dst = slot_addr + (unsigned)((s * TC + rg * RPI) * W * 4);
-                    if (nt) lds_dma_16B<true>(src, dst);
-                    else lds_dma_16B<false>(src, dst);
-                }
-            }
-        };
-
+        const Dma dma(a, col0, ldsf, wave - NWALK, threadIdx.x & 63);
         // prologue: tiles 0 .. R-2 in flight, wait for tile 0
 #pragma unroll
-        for (int m = 0; m < R - 1; ++m) issue_tile(T - (m + 1) * TC, m);
+        for (int m = 0; m < R - 1; ++m) dma.issue_tile(T - (m + 1) * TC, m);
         wait_vmcnt<(R - 2) * LPT>();
         __syncthreads();
         int slot = R - 1;                     // ring slot of tile k + R - 1
         for (int k = 0; k < nch; ++k) {
-            issue_tile(T - (k + R) * TC, slot);   // the slot the walker released at the last barrier
+            dma.issue_tile(T - (k + R) * TC, slot);   // the slot the walker released at the last barrier
             slot = slot + 1 == R ? 0 : slot + 1;
             wait_vmcnt<(R - 2) * LPT>();      // tile k+1 has landed; k+2 .. k+R-1 stay in flight
             __syncthreads();
@@ -495,29 +413,25 @@ __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_kernel(G
 //   producers: issue DMA of tile k+R-2 (into the slot of tile k-2) -> epilogue of tile k-1 ->
 //              counted wait until tile k+1 has landed -> barrier.
 // The ring therefore holds tiles k-1 .. k+R-2; the output tile is double buffered.
-// ring depth that fits the 160 KB of LDS for NF input fields (the deep-ring variants ask for more than the five-field
-// instances can hold: those run with the deepest ring that fits)
-constexpr int epi_ring_depth(int R, int NF, int TC, int W) {
-    return ((R * NF + 2) * TC * W * 4 <= 160 * 1024) ? R : (160 * 1024 / (TC * W * 4) - 2) / NF;
+// LDS of one instance: the ring plus the two output tiles.  Every shape that is built holds its
+// whole ring with all five input fields (static_assert in launch_dma_epi).
+constexpr size_t epi_lds_bytes(int R, int NF, int TC, int W) {
+    return ((size_t)R * NF + 2) * TC * W * sizeof(float);
 }
 
-template <int W, int NPROD, int TC, int R_, bool PTL, bool DENORM, bool ACT>
+template <int W, int NPROD, int TC, int R, bool PTL, bool DENORM, bool ACT>
 __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_epi_kernel(GaeArgs a) {
     constexpr int NWALK = (W + 63) / 64;
     constexpr int NF = 3 + (PTL ? 1 : 0) + (ACT ? 1 : 0);
-    constexpr int R = epi_ring_depth(R_, NF, TC, W);
-    constexpr int RPI = 256 / W;
-    constexpr int IPS = TC / RPI;
-    constexpr int LPT = NF * IPS / NPROD;          // DMA instructions per producer wave per tile
+    using Dma = TileDma<W, TC, NPROD, NF, PTL>;
+    constexpr int LPT = Dma::LPT;                  // DMA instructions per producer wave per tile
     constexpr int TILE = TC * W;                   // floats per field per tile
-    constexpr int TILE_FLOATS = NF * TILE;
+    constexpr int TILE_FLOATS = Dma::TILE_FLOATS;
     constexpr int V = W / 4;
     constexpr int GROUPS = TC * V;                 // float4 groups per tile
     constexpr int GPL = (GROUPS + NPROD * 64 - 1) / (NPROD * 64);   // groups per producer lane
-    static_assert(W <= 256 && (W <= 64 || W % 64 == 0), "strip width");
-    static_assert(TC % RPI == 0 && IPS % NPROD == 0, "row groups must split evenly over the producers");
     static_assert(R >= 3 && (R - 3) * LPT < 64, "ring depth vs the 6-bit vmcnt");
-    static_assert((R * TILE_FLOATS + 2 * TILE) * 4 <= 160 * 1024, "LDS ring + output tiles");
+    static_assert(epi_lds_bytes(R, NF, TC, W) <= 160 * 1024, "LDS ring + output tiles");
 
     extern __shared__ vf4 lds4[];                  // [R][NF][TC][V] ring, then [2][TC][V] output tiles
     float* ldsf = reinterpret_cast<float*>(lds4);
@@ -529,11 +443,8 @@ __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_epi_kern
     const long long C = a.C;
     zero_unowned_partials(a.partials, a.partial_rows, NPROD);
 
-    float sigma = 1.f, mu = 0.f;
-    if (DENORM) {
-        sigma = a.denorm[0];
-        mu = a.denorm[1];
-    }
+    float sigma, mu;
+    load_denorm(a, DENORM, sigma, mu);
 
     if (wave < NWALK) {
         // ---------------------------------------------------------------- walker
@@ -541,16 +452,7 @@ __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_epi_kern
         const int lc = NWALK > 1 ? wave * 64 + lane : lane;
         const long long col = col0 + lc;
         const bool live = lc < W && col < C;
-        float dv1 = 0.f, g = 0.f;
-        if (live) {
-            float nv = a.next_value[col];
-            a.value_preds[(long long)T * C + col] = nv;  // shared_buffer.py:187,218
-            dv1 = nv;
-            if (DENORM) {
-                float s = nv * sigma;
-                dv1 = s + mu;
-            }
-        }
+        float dv1 = walker_prologue(a, live, col, DENORM, sigma, mu), g = 0.f;
         const float gamma = a.gamma, gl = a.gl;
         constexpr int U = TC % 8 == 0 ? 8 : (TC % 4 == 0 ? 4 : (TC % 2 == 0 ? 2 : 1));
         __syncthreads();                                        // tile 0 landed
@@ -585,37 +487,10 @@ __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_epi_kern
         const int lane = threadIdx.x & 63;
         const int pw = wave - NWALK;
         const int ptid = pw * 64 + lane;                        // index among the producer lanes
-        const unsigned lds_base = (unsigned)(uintptr_t)ldsf;
-        const bool nt = (a.opts & 2) != 0;
+        const Dma dma(a, col0, ldsf, pw, lane);
         const bool has_adv = a.adv != nullptr;
-        const int r0 = lane / V;
-        const int c4 = lane - r0 * V;
-        long long lcol = col0 + c4 * 4;
-        if (lcol > C - 4) lcol = C - 4;
-        const float* fb0 = a.rewards + lcol;
-        const float* fb1 = a.value_preds + lcol;
-        const float* fb2 = a.masks + C + lcol;
-        const float* fb3 = (PTL ? a.bad + C : a.active) + lcol;
-        const float* fb4 = a.active + lcol;
         double s1 = 0.0, s2 = 0.0, cnt = 0.0;
 
-        auto issue_tile = [&](int tbase, int slot) {
-            const unsigned slot_addr = lds_base + (unsigned)slot * (TILE_FLOATS * 4);
-#pragma unroll
-            for (int s = 0; s < NF; ++s) {
-                const float* fbs = s == 0 ? fb0 : s == 1 ? fb1 : s == 2 ? fb2 : (s == 3 && PTL) ? fb3 : fb4;
-#pragma unroll
-                for (int q = 0; q < IPS / NPROD; ++q) {
-                    const int rg = pw + q * NPROD;
-                    int t = tbase + rg * RPI + r0;
-                    if (t < 0) t = 0;
-                    const float* src = fbs + (long long)t * C;
-                    const unsigned dst = slot_addr + (unsigned)((s * TC + rg * RPI) * W * 4);
-                    if (nt) lds_dma_16B<true>(src, dst);
-                    else lds_dma_16B<false>(src, dst);
-                }
-            }
-        };
         // epilogue of tile m (walked during the previous interval): returns / advantages / moments
         auto epilogue = [&](int m) {
             const int tbase = T - (m + 1) * TC;
@@ -658,71 +533,22 @@ __global__ void __launch_bounds__((NPROD + (W + 63) / 64) * 64) gae_dma_epi_kern
 
         // prologue: tiles 0 .. R-3 in flight, wait for tile 0
 #pragma unroll
-        for (int m = 0; m < R - 2; ++m) issue_tile(T - (m + 1) * TC, m);
+        for (int m = 0; m < R - 2; ++m) dma.issue_tile(T - (m + 1) * TC, m);
         wait_vmcnt<(R - 3) * LPT>();
         __syncthreads();
         int slot = R - 2;                     // ring slot of tile k + R - 2
         for (int k = 0; k < nch; ++k) {
-            issue_tile(T - (k + R - 1) * TC, slot);             // tile k+R-2 -> the slot tile k-2 has left
+            dma.issue_tile(T - (k + R - 1) * TC, slot);         // tile k+R-2 -> the slot tile k-2 has left
             slot = slot + 1 == R ? 0 : slot + 1;
             if (k >= 1) epilogue(k - 1);
             wait_vmcnt<(R - 3) * LPT>();                        // tile k+1 has landed
             __syncthreads();
         }
         epilogue(nch - 1);
-        if (a.partials != nullptr) {
-            s1 = wave_sum(s1);
-            s2 = wave_sum(s2);
-            cnt = wave_sum(cnt);
-            if (lane == 0) {
-                double* p = a.partials + ((long long)blockIdx.x * NPROD + pw) * 3;
-                p[0] = s1;
-                p[1] = s2;
-                p[2] = cnt;
-            }
-        }
+        write_partials(a, (long long)blockIdx.x * NPROD + pw, lane, s1, s2, cnt);
         wait_vmcnt<0>();
     }
 }
-
-// ---- "coop" kernel: every wave loads, wave 0 walks, single LDS tile (small strips) ---------
-template <int W, int NWAVES, int TC, bool PTL, bool DENORM, bool ACT>
-__global__ void __launch_bounds__(NWAVES * 64) gae_strip_kernel(GaeArgs a) {
-    MAPPO_TILE_CONSTS(W, TC, NWAVES * 64, PTL, ACT)
-    extern __shared__ vf4 lds4[];            // [NF][TC][V]
-    const int tid = threadIdx.x;
-    const long long col0 = (long long)blockIdx.x * W;
-    const int T = a.T;
-    const int lane = tid;
-    const long long col = col0 + lane;
-    const bool walker = tid < 64;
-    const bool live = walker && lane < W && col < a.C;
-
-    vf4 pre[NF][PER];
-    float sigma, mu, dv1, g = 0.f;
-    double s1 = 0.0, s2 = 0.0, cnt = 0.0;
-    walker_prologue(a, live, col, DENORM, sigma, mu, dv1);
-
-    const int nch = (T + TC - 1) / TC;
-    MAPPO_LOAD_TILE(pre, tid, T - TC)
-    for (int k = 0; k < nch; ++k) {
-        const int tbase = T - (k + 1) * TC;
-        MAPPO_STASH_TILE(pre, tid, lds4)
-        __syncthreads();
-        MAPPO_LOAD_TILE(pre, tid, tbase - TC)    // in flight while wave 0 walks this tile
-        if (walker)
-            walk_tile<W, TC, PTL, DENORM, ACT>(a, reinterpret_cast<const float*>(lds4), lane, col, live,
-                                               tbase, sigma, mu, g, dv1, s1, s2, cnt);
-        __syncthreads();
-    }
-    zero_unowned_partials(a.partials, a.partial_rows);
-    if (walker) walker_epilogue(a, lane, s1, s2, cnt);
-}
-
-#undef MAPPO_LOAD_TILE
-#undef MAPPO_STASH_TILE
-#undef MAPPO_SLOT_BASE
-#undef MAPPO_TILE_CONSTS
 
 // ----------------------------------------------------------------- column kernel ----
 // One lane per column, any C, all seven reference branches.
@@ -735,11 +561,8 @@ __global__ void __launch_bounds__(64) gae_column_kernel(GaeArgs a) {
     const bool has_act = a.active != nullptr;
     const bool has_adv = a.adv != nullptr;
 
-    float sigma = 1.f, mu = 0.f;
-    if (DENORM) {
-        sigma = a.denorm[0];
-        mu = a.denorm[1];
-    }
+    float sigma, mu;
+    load_denorm(a, DENORM, sigma, mu);
     const float gamma = a.gamma, gl = a.gl;
     double s1 = 0.0, s2 = 0.0, cnt = 0.0;
 
@@ -813,23 +636,12 @@ __global__ void __launch_bounds__(64) gae_column_kernel(GaeArgs a) {
         }
     }
     zero_unowned_partials(a.partials, a.partial_rows);
-    if (a.partials != nullptr) {
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        cnt = wave_sum(cnt);
-        if (threadIdx.x == 0) {
-            double* p = a.partials + (long long)blockIdx.x * 3;
-            p[0] = s1;
-            p[1] = s2;
-            p[2] = cnt;
-        }
-    }
+    write_partials(a, blockIdx.x, threadIdx.x, s1, s2, cnt);
 }
 
-// ------------------------------------------------------- K5: moments and stats ----
 // ------------------------------------------------------------------ time-parallel scan ----
 // Narrow buffers (C = N * A of a few thousand columns: cfg2, SMAC, one rank's shard of a data-parallel job) do not
-// have enough columns to hide a 200 .. 400-step serial walk: the strip kernels above sit on a ~40-60 us latency floor
+// have enough columns to hide a 200 .. 400-step serial walk: the ring kernels above sit on a ~40-60 us latency floor
 // whatever the byte count.  The recurrence g_t = delta_t + c_t * g_{t+1} is an affine map in g, and affine maps
 // compose: a segment [t0, t1) acts as g_{t0} = Q + P * g_{t1} with (P, Q) computable without knowing g_{t1}.
 // A workgroup takes 32 columns x all T steps; T is cut into 16 segments, one per half-wave (8 waves x 2).  Every lane
@@ -842,12 +654,11 @@ __global__ void __launch_bounds__(64) gae_column_kernel(GaeArgs a) {
 // Only the 15 segment-boundary values carry the re-association error of step 3 (a few ulp); everything inside a segment
 // is the bit-exact recurrence started from them.  Hence "tolerance mode": results agree with the reference to ~1e-6
 // relative instead of bit for bit, which is what BASELINE.json's north star asks of returns / advantages.  Selected for
-// 2048 <= C < 16384 (wide buffers keep the bit-exact strip kernels; MAPPO_GAE_EXACT forces them everywhere).
+// 2048 <= C < 16384 (wide buffers keep the bit-exact ring kernels; MAPPO_GAE_EXACT forces them everywhere).
 constexpr int kScanSegs = 16;
 constexpr int kScanLmax = 26;      // steps per segment held in registers: T <= 416
 
-// W columns per workgroup, 64 / W segments per wave: W = 16 -> 4 waves, 64-byte row pieces, C / 16 workgroups;
-// W = 32 -> 8 waves, 128-byte pieces; W = 64 -> 16 waves, 256-byte pieces
+// W columns per workgroup, 64 / W segments per wave.  Built for W = 32: 8 waves, 128-byte row pieces, C / 32 workgroups.
 template <int W, bool PTL, bool DENORM, bool ACT>
 __global__ void __launch_bounds__(W * kScanSegs) gae_scan_kernel(GaeArgs a) {
     constexpr int kScanCols = W;
@@ -867,11 +678,8 @@ __global__ void __launch_bounds__(W * kScanSegs) gae_scan_kernel(GaeArgs a) {
     if (n > Ls) n = Ls;
     if (n < 0) n = 0;
     const bool has_adv = a.adv != nullptr;
-    float sigma = 1.f, mu = 0.f;
-    if (DENORM) {
-        sigma = a.denorm[0];
-        mu = a.denorm[1];
-    }
+    float sigma, mu;
+    load_denorm(a, DENORM, sigma, mu);
     const float gamma = a.gamma, gl = a.gl;
 
     // ---- 1. the whole segment into registers
@@ -974,6 +782,7 @@ __global__ void __launch_bounds__(W * kScanSegs) gae_scan_kernel(GaeArgs a) {
     }
 }
 
+// ------------------------------------------------------- K5: moments and stats ----
 __global__ void __launch_bounds__(256) adv_reduce_kernel(const double* partials, long long rows,
                                                           double* sums) {
     __shared__ double sh[3][256];
@@ -1064,23 +873,35 @@ __global__ void __launch_bounds__(256) advantages_kernel(const float* ret, const
 int g_variant = 0;
 int g_last_variant = 0;
 
-template <int W>
-hipError_t launch_scan(const GaeArgs& a, unsigned flags, hipStream_t stream) {
-    const bool ptl = flags & MAPPO_GAE_PROPER_TIME_LIMITS, dn = flags & MAPPO_GAE_DENORM, act = a.active != nullptr;
-    const dim3 grid((unsigned)((a.C + W - 1) / W)), block(W * kScanSegs);
-#define MAPPO_SCAN_CASE(P_, D_, A_)                                                               \
-    if (ptl == P_ && dn == D_ && act == A_) {                                                     \
-        hipLaunchKernelGGL((gae_scan_kernel<W, P_, D_, A_>), grid, block, 0, stream, a);          \
-        return hipGetLastError();                                                                 \
+// Three runtime flags -> compile-time booleans: f(std::bool_constant<b0>, <b1>, <b2>) for the given values.  Every
+// launcher below picks its template instance through this.
+template <class F>
+hipError_t with_flags(bool b0, bool b1, bool b2, F&& f) {
+    using Y = std::true_type;
+    using N = std::false_type;
+    switch ((b0 ? 4 : 0) | (b1 ? 2 : 0) | (b2 ? 1 : 0)) {
+        case 0: return f(N(), N(), N());
+        case 1: return f(N(), N(), Y());
+        case 2: return f(N(), Y(), N());
+        case 3: return f(N(), Y(), Y());
+        case 4: return f(Y(), N(), N());
+        case 5: return f(Y(), N(), Y());
+        case 6: return f(Y(), Y(), N());
+        default: return f(Y(), Y(), Y());
     }
-    MAPPO_SCAN_CASE(false, false, false) MAPPO_SCAN_CASE(false, false, true) MAPPO_SCAN_CASE(false, true, false)
-    MAPPO_SCAN_CASE(false, true, true) MAPPO_SCAN_CASE(true, false, false) MAPPO_SCAN_CASE(true, false, true)
-    MAPPO_SCAN_CASE(true, true, false) MAPPO_SCAN_CASE(true, true, true)
-#undef MAPPO_SCAN_CASE
-    return hipErrorInvalidValue;
 }
 
-// Measurement hook (mappo_gae_time_next_launch): the next launch of a strip / LDS-DMA kernel carries the library's own event
+// (time limits, denorm, active masks) of a GAE launch
+template <class F>
+hipError_t with_gae_flags(const GaeArgs& a, unsigned flags, F&& f) {
+    return with_flags(flags & MAPPO_GAE_PROPER_TIME_LIMITS, flags & MAPPO_GAE_DENORM, a.active != nullptr, f);
+}
+
+inline int gae_slots(const GaeArgs& a, unsigned flags) {
+    return 3 + ((flags & MAPPO_GAE_PROPER_TIME_LIMITS) ? 1 : 0) + (a.active ? 1 : 0);
+}
+
+// Measurement hook (mappo_gae_time_next_launch): the next launch of an LDS-DMA ring kernel carries the library's own event
 // pair AT DISPATCH LEVEL (hipExtLaunchKernelGGL: the events take the kernel's begin and end timestamps -- what rocprofv3's
 // kernel trace reports).  A pair of hipEventRecord calls around the launch brackets two more packets of the command processor:
 // + 5-6 us on this 50 us kernel, measured against the trace of the same run (profiles/r06_gae_in_situ_timing.json).
@@ -1089,8 +910,14 @@ hipEvent_t g_time_begin[kTimeSlots], g_time_end[kTimeSlots];
 bool g_time_made[kTimeSlots], g_time_taken[kTimeSlots];
 int g_time_armed = -1, g_time_next = 0;
 
+// Launch of a ring kernel.  More than 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU) is granted once per (device,
+// kernel) by mappo::grant_lds, which keeps the attribute call out of every later launch.
 template <typename K>
-inline void launch_gae(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const GaeArgs& a) {
+hipError_t launch_gae(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const GaeArgs& a) {
+    if (lds > 64 * 1024) {
+        const hipError_t e = mappo::grant_lds(kernel, lds);
+        if (e != hipSuccess) return e;
+    }
     if (g_time_armed >= 0) {
         const int s = g_time_armed;
         g_time_armed = -1;
@@ -1099,87 +926,35 @@ inline void launch_gae(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t 
     } else {
         hipLaunchKernelGGL(kernel, grid, block, lds, stream, a);
     }
-}
-
-#define MAPPO_DISPATCH_FLAGS(KERNEL, ...)                                                        \
-    do {                                                                                         \
-        const bool ptl = flags & MAPPO_GAE_PROPER_TIME_LIMITS;                                   \
-        const bool den = flags & MAPPO_GAE_DENORM;                                               \
-        const bool act = a.active != nullptr;                                                    \
-        const int sel = (ptl ? 4 : 0) | (den ? 2 : 0) | (act ? 1 : 0);                           \
-        switch (sel) {                                                                           \
-            case 0: launch_gae((KERNEL<__VA_ARGS__, false, false, false>), grid, block, lds, stream, a); break; \
-            case 1: launch_gae((KERNEL<__VA_ARGS__, false, false, true>), grid, block, lds, stream, a); break;  \
-            case 2: launch_gae((KERNEL<__VA_ARGS__, false, true, false>), grid, block, lds, stream, a); break;  \
-            case 3: launch_gae((KERNEL<__VA_ARGS__, false, true, true>), grid, block, lds, stream, a); break;   \
-            case 4: launch_gae((KERNEL<__VA_ARGS__, true, false, false>), grid, block, lds, stream, a); break;  \
-            case 5: launch_gae((KERNEL<__VA_ARGS__, true, false, true>), grid, block, lds, stream, a); break;   \
-            case 6: launch_gae((KERNEL<__VA_ARGS__, true, true, false>), grid, block, lds, stream, a); break;   \
-            default: launch_gae((KERNEL<__VA_ARGS__, true, true, true>), grid, block, lds, stream, a); break;   \
-        }                                                                                        \
-    } while (0)
-
-inline int gae_slots(const GaeArgs& a, unsigned flags) {
-    return 3 + ((flags & MAPPO_GAE_PROPER_TIME_LIMITS) ? 1 : 0) + (a.active ? 1 : 0);
-}
-
-template <int W, int NWAVES, int TC>
-hipError_t launch_strip(const GaeArgs& a, unsigned flags, hipStream_t stream) {
-    const size_t lds = (size_t)gae_slots(a, flags) * TC * W * sizeof(float);
-    dim3 grid((unsigned)((a.C + W - 1) / W)), block(NWAVES * 64);
-    MAPPO_DISPATCH_FLAGS(gae_strip_kernel, W, NWAVES, TC);
     return hipGetLastError();
 }
 
 template <int W, int NPROD, int TC, int R>
 hipError_t launch_dma(const GaeArgs& a, unsigned flags, hipStream_t stream) {
     const size_t lds = (size_t)R * gae_slots(a, flags) * TC * W * sizeof(float);
-    dim3 grid((unsigned)((a.C + W - 1) / W)), block((NPROD + (W + 63) / 64) * 64);
-    if (lds > 64 * 1024) {   // opt in to more than 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU)
-        const bool ptl = flags & MAPPO_GAE_PROPER_TIME_LIMITS;
-        const bool den = flags & MAPPO_GAE_DENORM;
-        const bool act = a.active != nullptr;
-#define MAPPO_SET_LDS(P, D, A_)                                                                   \
-        if (ptl == P && den == D && act == A_)                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gae_dma_kernel<W, NPROD, TC, R, P, D, A_>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        MAPPO_SET_LDS(false, false, false) MAPPO_SET_LDS(false, false, true) MAPPO_SET_LDS(false, true, false)
-        MAPPO_SET_LDS(false, true, true) MAPPO_SET_LDS(true, false, false) MAPPO_SET_LDS(true, false, true)
-        MAPPO_SET_LDS(true, true, false) MAPPO_SET_LDS(true, true, true)
-#undef MAPPO_SET_LDS
-    }
-    MAPPO_DISPATCH_FLAGS(gae_dma_kernel, W, NPROD, TC, R);
-    return hipGetLastError();
+    const dim3 grid((unsigned)((a.C + W - 1) / W)), block((NPROD + (W + 63) / 64) * 64);
+    return with_gae_flags(a, flags, [&](auto ptl, auto den, auto act) {
+        return launch_gae(gae_dma_kernel<W, NPROD, TC, R, ptl(), den(), act()>, grid, block, lds, stream, a);
+    });
 }
 
 template <int W, int NPROD, int TC, int R>
 hipError_t launch_dma_epi(const GaeArgs& a, unsigned flags, hipStream_t stream) {
-    const int nf = gae_slots(a, flags);
-    const size_t lds = ((size_t)epi_ring_depth(R, nf, TC, W) * nf + 2) * TC * W * sizeof(float);
-    dim3 grid((unsigned)((a.C + W - 1) / W)), block((NPROD + (W + 63) / 64) * 64);
-    if (lds > 64 * 1024) {
-        const bool ptl = flags & MAPPO_GAE_PROPER_TIME_LIMITS;
-        const bool den = flags & MAPPO_GAE_DENORM;
-        const bool act = a.active != nullptr;
-#define MAPPO_SET_LDS(P, D, A_)                                                                   \
-        if (ptl == P && den == D && act == A_)                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gae_dma_epi_kernel<W, NPROD, TC, R, P, D, A_>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        MAPPO_SET_LDS(false, false, false) MAPPO_SET_LDS(false, false, true) MAPPO_SET_LDS(false, true, false)
-        MAPPO_SET_LDS(false, true, true) MAPPO_SET_LDS(true, false, false) MAPPO_SET_LDS(true, false, true)
-        MAPPO_SET_LDS(true, true, false) MAPPO_SET_LDS(true, true, true)
-#undef MAPPO_SET_LDS
-    }
-    MAPPO_DISPATCH_FLAGS(gae_dma_epi_kernel, W, NPROD, TC, R);
-    return hipGetLastError();
+    static_assert(epi_lds_bytes(R, 5, TC, W) <= 160 * 1024, "the ring must fit with all five input fields");
+    const size_t lds = epi_lds_bytes(R, gae_slots(a, flags), TC, W);
+    const dim3 grid((unsigned)((a.C + W - 1) / W)), block((NPROD + (W + 63) / 64) * 64);
+    return with_gae_flags(a, flags, [&](auto ptl, auto den, auto act) {
+        return launch_gae(gae_dma_epi_kernel<W, NPROD, TC, R, ptl(), den(), act()>, grid, block, lds, stream, a);
+    });
 }
 
-template <int W, int NPROD, int TC, int NBUF>
-hipError_t launch_pipe(const GaeArgs& a, unsigned flags, hipStream_t stream) {
-    const size_t lds = (size_t)2 * gae_slots(a, flags) * TC * W * sizeof(float);
-    dim3 grid((unsigned)((a.C + W - 1) / W)), block((NPROD + 1) * 64);
-    MAPPO_DISPATCH_FLAGS(gae_pipe_kernel, W, NPROD, TC, NBUF);
-    return hipGetLastError();
+template <int W>
+hipError_t launch_scan(const GaeArgs& a, unsigned flags, hipStream_t stream) {
+    const dim3 grid((unsigned)((a.C + W - 1) / W)), block(W * kScanSegs);
+    return with_gae_flags(a, flags, [&](auto ptl, auto den, auto act) {
+        hipLaunchKernelGGL((gae_scan_kernel<W, ptl(), den(), act()>), grid, block, 0, stream, a);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------- MAT kernel ----
@@ -1226,11 +1001,8 @@ __global__ void __launch_bounds__(64) gae_mat_kernel(GaeArgs a, int A) {
     const long long col = (long long)blockIdx.x * 64 + threadIdx.x;
     const bool live = col < C;
     const bool has_act = a.active != nullptr;
-    float sigma = 1.f, mu = 0.f;
-    if (DENORM) {
-        sigma = a.denorm[0];
-        mu = a.denorm[1];
-    }
+    float sigma, mu;
+    load_denorm(a, DENORM, sigma, mu);
     const float gamma = a.gamma, gl = a.gl, fA = (float)A;
     double s1 = 0.0, s2 = 0.0, cnt = 0.0;
     if (live) {
@@ -1276,39 +1048,17 @@ __global__ void __launch_bounds__(64) gae_mat_kernel(GaeArgs a, int A) {
         }
     }
     zero_unowned_partials(a.partials, a.partial_rows);
-    if (a.partials != nullptr) {
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        cnt = wave_sum(cnt);
-        if (threadIdx.x == 0) {
-            double* p = a.partials + (long long)blockIdx.x * 3;
-            p[0] = s1;
-            p[1] = s2;
-            p[2] = cnt;
-        }
-    }
+    write_partials(a, blockIdx.x, threadIdx.x, s1, s2, cnt);
 }
 
 hipError_t launch_column(const GaeArgs& a, unsigned flags, hipStream_t stream) {
-    const bool gae = flags & MAPPO_GAE_USE_GAE;
-    const bool ptl = flags & MAPPO_GAE_PROPER_TIME_LIMITS;
-    const bool den = flags & MAPPO_GAE_DENORM;
-    dim3 grid((unsigned)((a.C + 63) / 64)), block(64);
-#define MAPPO_COL(G, P, D) \
-    hipLaunchKernelGGL((gae_column_kernel<G, P, D>), grid, block, 0, stream, a)
-    if (gae) {
-        if (ptl && den) MAPPO_COL(true, true, true);
-        else if (ptl) MAPPO_COL(true, true, false);
-        else if (den) MAPPO_COL(true, false, true);
-        else MAPPO_COL(true, false, false);
-    } else {
-        if (ptl && den) MAPPO_COL(false, true, true);
-        else if (ptl) MAPPO_COL(false, true, false);
-        else if (den) MAPPO_COL(false, false, true);  // D() only enters the fused advantages here
-        else MAPPO_COL(false, false, false);
-    }
-#undef MAPPO_COL
-    return hipGetLastError();
+    const dim3 grid((unsigned)((a.C + 63) / 64)), block(64);
+    // (without GAE, D() only enters the fused advantages)
+    return with_flags(flags & MAPPO_GAE_USE_GAE, flags & MAPPO_GAE_PROPER_TIME_LIMITS, flags & MAPPO_GAE_DENORM,
+                      [&](auto gae, auto ptl, auto den) {
+                          hipLaunchKernelGGL((gae_column_kernel<gae(), ptl(), den()>), grid, block, 0, stream, a);
+                          return hipGetLastError();
+                      });
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -1409,8 +1159,8 @@ extern "C" int mappo_gae_f32(const float* rewards, float* value_preds, const flo
     if (!strip_ok) variant = 99;
     // narrow buffers: the time-parallel scan (tolerance mode) unless the caller insists on bit-exact results
     const bool scan_ok = strip_ok && T <= kScanSegs * kScanLmax && (!a.partials || a.partial_rows >= (C + 31) / 32);
-    if (variant == 71) variant = 70;
-    if (variant >= 70 && variant <= 72 && !scan_ok) variant = 0;
+    if (variant == 71 || variant == 72) variant = 70;   // the 64- and 16-column scans are gone: aliases of the one that is built
+    if (variant == 70 && !scan_ok) variant = 0;
     if (variant == 0 && scan_ok && !(flags & MAPPO_GAE_EXACT) && C >= 2048 && C < 16384 && T >= 64) variant = 70;
     if (variant == 0) {
         // LDS-DMA ring kernel; strip width by column count so that >= 256 workgroups exist;
@@ -1420,37 +1170,18 @@ extern "C" int mappo_gae_f32(const float* rewards, float* value_preds, const flo
     }
 
     g_last_variant = variant;
-    hipError_t e;
+    // The kernels the automatic choice can reach, plus 99 for the column kernel.  Any other number -- among them those of
+    // the tuning variants that are no longer built -- has no case and runs the column kernel.
     switch (variant) {
-        // cooperative strip (all waves load, wave 0 walks): the simplest LDS-staged form
-        case 2: e = launch_strip<64, 4, 32>(a, flags, stream); break;
-        case 6: e = launch_strip<16, 1, 64>(a, flags, stream); break;
-        // register-prefetch pipe (1 walker + 4 producers, 2 tiles in flight in VGPRs)
-        case 20: e = launch_pipe<64, 4, 32, 2>(a, flags, stream); break;
         // LDS-DMA ring, walker does the epilogue
-        case 33: e = launch_dma<64, 2, 16, 3>(a, flags, stream); break;
-        case 34: e = launch_dma<32, 1, 16, 4>(a, flags, stream); break;
-        case 36: e = launch_dma<16, 1, 16, 4>(a, flags, stream); break;
-        case 42: e = launch_dma<128, 2, 8, 3>(a, flags, stream); break;
-        // LDS-DMA ring, epilogue on the producer waves (defaults)
-        case 51: e = launch_dma_epi<128, 4, 8, 4>(a, flags, stream); break;
-        case 54: e = launch_dma_epi<64, 2, 16, 4>(a, flags, stream); break;
-        case 56: e = launch_dma_epi<32, 2, 16, 4>(a, flags, stream); break;
-        case 57: e = launch_dma_epi<128, 6, 12, 4>(a, flags, stream); break;
-        // (r6) deeper rings: with R = 4 a producer's counted wait leaves ~1.5 tiles (37 KB per CU, 9 MB chip-wide) in
-        // flight -- the epilogue's stores sit between the DMA issues in the counter -- which is what a 5.4 TB/s stream
-        // with ~1.7 us of loaded latency needs, and no more
-        case 58: e = launch_dma_epi<128, 6, 12, 5>(a, flags, stream); break;
-        case 59: e = launch_dma_epi<128, 6, 12, 6>(a, flags, stream); break;
-        case 60: e = launch_dma_epi<128, 4, 8, 6>(a, flags, stream); break;
-        case 61: e = launch_dma_epi<128, 8, 16, 4>(a, flags, stream); break;
-        case 62: e = launch_dma_epi<128, 4, 8, 8>(a, flags, stream); break;
-        case 70: e = launch_scan<32>(a, flags, stream); break;
-        // (71, the 64-column form, is gone: never selected automatically, and three of its instances spilled 68-196 bytes per lane)
-        case 72: e = launch_scan<16>(a, flags, stream); break;
-        default: e = launch_column(a, flags, stream); break;
+        case 36: return (int)launch_dma<16, 1, 16, 4>(a, flags, stream);
+        // LDS-DMA ring, epilogue on the producer waves
+        case 54: return (int)launch_dma_epi<64, 2, 16, 4>(a, flags, stream);
+        case 56: return (int)launch_dma_epi<32, 2, 16, 4>(a, flags, stream);
+        case 57: return (int)launch_dma_epi<128, 6, 12, 4>(a, flags, stream);
+        case 70: return (int)launch_scan<32>(a, flags, stream);
+        default: return (int)launch_column(a, flags, stream);
     }
-    return (int)e;
 }
 
 extern "C" int mappo_gae_mat_f32(const float* rewards, float* value_preds, const float* next_value,

@@ -4,6 +4,9 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <map>
+#include <mutex>
+#include <utility>
 
 namespace mappo {
 
@@ -19,6 +22,28 @@ inline int row_vec(const void* src, const void* dst, long long width) {
     if (width % 4 == 0 && aligned_to(src, 16) && aligned_to(dst, 16)) return 4;
     if (width % 2 == 0 && aligned_to(src, 8) && aligned_to(dst, 8)) return 2;
     return 1;
+}
+
+// Dynamic LDS above 48 KB has to be granted per kernel function before the launch.  Granted once per kernel and size: the
+// attribute call is kept out of the launch path -- in particular out of launches that are being captured into a HIP graph
+// from the autograd thread (onpolicy/algorithms/r_mappo/update_graph.py).  Returns the failed attribute call's error.
+template <class K>
+hipError_t grant_lds(K kernel, size_t bytes) {
+    if (bytes <= 48 * 1024) return hipSuccess;
+    // the attribute belongs to (device, function): a process that drives two GPUs must be granted on both
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, size_t> granted;
+    const void* fn = reinterpret_cast<const void*>(kernel);
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) device = -1;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& have = granted[std::make_pair(device, fn)];
+    if (bytes > have) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+        if (device >= 0) have = bytes;
+    }
+    return hipSuccess;
 }
 
 // Source-row mapping of the samplers (shared by the tile gather and the standardising gather).

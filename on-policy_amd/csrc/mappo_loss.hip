@@ -265,7 +265,7 @@ extern "C" int mappo_ppo_loss_f32(const mappo_ppo_loss_t* args, mappo_stream_t s
         if (lds > 48 * 1024) {
             const void* fn = avail ? reinterpret_cast<const void*>(&ppo_loss_kernel<true, true, 0>)
                                    : reinterpret_cast<const void*>(&ppo_loss_kernel<false, true, 0>);
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            hipError_t e = mappo::grant_lds(fn, lds);   // once per (device, kernel), not per launch
             if (e != hipSuccess) return (int)e;
         }
         const bool small = a.n_actions <= 8;

@@ -204,32 +204,13 @@ __device__ __forceinline__ float* lds() {
 
 namespace {
 int g_launch_error = 0;
-// dynamic LDS above 64 KB has to be granted per kernel function before the launch
-// (granted once per kernel and size: the attribute call is kept out of the launch path -- in particular out of launches that
-// are being captured into a HIP graph from the autograd thread, onpolicy/algorithms/r_mappo/update_graph.py)
-template <class K>
-void grant_lds(K kernel, size_t bytes) {
-    if (bytes > 48 * 1024) {
-        // the attribute belongs to (device, function): a process that drives two GPUs must be granted on both
-        static std::mutex mu;
-        static std::map<std::pair<int, const void*>, size_t> granted;
-        const void* fn = reinterpret_cast<const void*>(kernel);
-        int device = 0;
-        if (hipGetDevice(&device) != hipSuccess) device = -1;
-        std::lock_guard<std::mutex> lock(mu);
-        size_t& have = granted[std::make_pair(device, fn)];
-        if (bytes > have) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-            if (e != hipSuccess) g_launch_error = (int)e;
-            else if (device >= 0) have = bytes;
-        }
-    }
-}
 }  // namespace
 
+// (mappo::grant_lds: dynamic LDS above 48 KB is granted once per kernel, outside the launch path)
 #define MAPPO_LAUNCH(kernel, grid, block, lds_bytes, stream, ...)                                      \
     do {                                                                                               \
-        grant_lds(kernel, (lds_bytes));                                                                \
+        const hipError_t grant_ = mappo::grant_lds(kernel, (lds_bytes));                               \
+        if (grant_ != hipSuccess) g_launch_error = (int)grant_;                                        \
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), (lds_bytes), stream, __VA_ARGS__);         \
     } while (0)
 #define MAPPO_LAUNCH_ERROR() (g_launch_error ? g_launch_error : (int)hipGetLastError())

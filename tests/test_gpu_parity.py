@@ -96,18 +96,20 @@ def test_gae_matrix_vs_reference(gold, variant):
         lib.mappo_gae_set_variant(old)
 
 
-# ------------------------------------------------------------------ K1 vs oracle, every variant
+# ------------------------------------------------------------------ K1 vs oracle, every kernel that is built
 def _random_case(T, N, A, seed, device):
     rng = np.random.default_rng(seed)
     arrays = fill_buffer_arrays(buffer_shapes(T, N, A, 3, 4, 5, 8), rng, na=5, p_mask=1.0 - 1.0 / 25)
     return arrays
 
 
-@pytest.mark.parametrize("variant", [2, 6, 20, 33, 34, 36, 42, 51, 54, 56, 57, 3033, 3042, 3057, 2057, 1054, 99])
+@pytest.mark.parametrize("variant", [2, 20, 33, 36, 54, 56, 57, 3036, 3042, 3054, 3056, 3057, 2057, 1054, 99])
 @pytest.mark.parametrize("ptl,norm", [(False, True), (True, True), (False, False), (True, False)])
 def test_gae_variants_vs_oracle(variant, ptl, norm):
-    """Every kernel variant is bit-identical to the oracle, including ragged strips (C % W != 0),
-    T not a multiple of the tile length and T smaller than a tile."""
+    """Every kernel the dispatcher can choose -- the four ring shapes, plain and with the option bits the automatic
+    choice sets (30xx), and the column kernel -- is bit-identical to the oracle, including ragged strips (C % W != 0),
+    T not a multiple of the tile length and T smaller than a tile.  2, 20, 33 and 3042 are numbers of tuning variants that
+    are no longer built: a number without a kernel of its own runs the column kernel and must give the same bits."""
     lib = _native_lib()
     old = lib.mappo_gae_set_variant(variant)
     try:
@@ -168,7 +170,7 @@ def test_gae_north_star_size_vs_oracle():
     nvd = torch.from_numpy(nv).to(dev)
     exp_ret, exp_v = oracle.compute_returns(arrays["rewards"], arrays["value_preds"], nv, arrays["masks"],
                                             sigma=sigma, mu=mu, denorm=True)
-    for variant in (0, 2, 20, 33, 57, 99):
+    for variant in (0, 54, 57, 3057, 99):
         lib.mappo_gae_set_variant(variant)
         ret.zero_()
         code = lib.mappo_gae_f32(t["rewards"].data_ptr(), t["value_preds"].data_ptr(), nvd.data_ptr(),
