@@ -751,6 +751,25 @@ int mappo_simple_reference_step(double* pos, double* vel, double* landmarks, int
                                 double* per_agent, int64_t n_worlds, int world_length, int auto_reset,
                                 mappo_stream_t stream);
 
+/* ---------------------------------------------- K11 family: simple_speaker_listener worlds on the device ----
+ * One env step of `n_worlds` speaker / listener worlds (reference onpolicy/envs/mpe/scenarios/simple_speaker_listener.py
+ * :38-98, environment.py:115-255, core.py:160-190 and :207-288; 2 agents, 3 landmarks, no contacts) as one launch.
+ * Agent 0 (the speaker) never moves; agent 1 (the listener) is silent.  State is updated in place: pos / vel [n, 2, 2]
+ * and landmarks [n, 3, 2] float64, t [n] int64, goal [n] int64 (the goal landmark, 0..2), comm [n] int64 (the speaker's
+ * last symbol, -1 = silent).  actions [n, 2] int64 (the speaker's symbol 0..2, the listener's movement 0..4).  Worlds
+ * whose t reaches world_length report done and (auto_reset) restart from fresh_pos [n, 2, 2], fresh_landmarks [n, 3, 2]
+ * (uniform(-1, 1) draws) and fresh_goal [n], at rest and silent.  Outputs: obs [n, 14] float32, one row per world that
+ * is also the centralised observation: columns 0:3 the speaker's observation (the goal landmark's colour), 3:14 the
+ * listener's (velocity, landmarks relative to it, the speaker's symbol one-hot).  obs is written after a restart, so a
+ * restarted world reports its fresh state; rewards, dones and per_agent are those of the step that ended the episode.
+ * rewards [n, 2, 1] float32 (shared: -2 |listener - goal|^2), dones [n, 2] bytes, per_agent [n, 2] float64
+ * (-|listener - goal|^2, the individual_reward info). */
+int mappo_simple_speaker_listener_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,
+                                       int64_t* comm, const int64_t* actions, const double* fresh_pos,
+                                       const double* fresh_landmarks, const int64_t* fresh_goal, float* obs,
+                                       float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
+                                       int world_length, int auto_reset, mappo_stream_t stream);
+
 /* --------------------------------------------------------------------- misc ---- */
 int         mappo_abi_version(void);
 const char* mappo_build_info(void);        /* "gfx950 ..." static string */

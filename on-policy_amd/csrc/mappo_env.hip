@@ -31,7 +31,7 @@ struct World {
     long long* t;               // [N]
     const double* fresh_pos;    // [N, A, 2] uniform(-1, 1)
     const double* fresh_land;   // [N, L, 2] uniform(-1, 1)
-    float* obs;                 // [N, A, Do]
+    float* obs;                 // [N, A, Do] ([N, sum Do] where the agents' observations differ in width)
     float* rew;                 // [N, A, 1]
     unsigned char* done;        // [N, A] (bool)
     double* per_agent;          // [N, A]
@@ -75,13 +75,14 @@ __device__ __forceinline__ void action_force(long long mv, double& fx, double& f
     fy = (mv == 3 ? 1.0 : mv == 4 ? -1.0 : 0.0) * kSens;
 }
 
-// core.py:160-175: damping, then force * dt, then the position; no mass / max speed in these scenarios
+// core.py:160-175: damping, then force * dt, then the position; no mass / max speed in these scenarios.  Agents before
+// `first` are not movable (core.py:162) and keep their position and velocity
 template <int MA>
 __device__ __forceinline__ void integrate(int A, double (&px)[MA], double (&py)[MA], double (&vx)[MA], double (&vy)[MA],
-                                          const double (&fx)[MA], const double (&fy)[MA]) {
+                                          const double (&fx)[MA], const double (&fy)[MA], int first = 0) {
 #pragma unroll
     for (int i = 0; i < MA; ++i) {
-        if (i >= A) continue;
+        if (i < first || i >= A) continue;
         vx[i] = vx[i] * (1 - kDamping) + fx[i] * kDt;
         vy[i] = vy[i] * (1 - kDamping) + fy[i] * kDt;
         px[i] = px[i] + vx[i] * kDt;
@@ -322,6 +323,70 @@ __global__ void __launch_bounds__(64) reference_step_kernel(RefArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// simple_speaker_listener (scenarios/simple_speaker_listener.py): agent 0, the speaker, does not move and sees the colour
+// of the goal landmark; agent 1, the listener, is silent and has to reach it.  One goal and one communication symbol per
+// world (the speaker's; -1: silent), advanced in place like simple_reference's.  The observation leaves as ONE row per
+// world, speaker's columns first: what the centralised critic reads, and column views of it are the agents' own.
+constexpr int kSpkAgents = 2, kSpkLandmarks = 3, kSpkSymbols = 3, kSpeaker = 0, kListener = 1;
+constexpr int kSpkObs = 3 + (2 + 2 * kSpkLandmarks + kSpkSymbols);     // 3 + 11 = 14
+
+struct SpeakerArgs {
+    World s;                        // s.obs: [N, 14]
+    long long* goal;                // [N] goal landmark, 0..2
+    long long* comm;                // [N] the speaker's last symbol, -1 = silent
+    const long long* act;           // [N, 2] (the speaker's symbol 0..2, the listener's movement 0..4)
+    const long long* fresh_goal;    // [N] 0..2
+};
+
+__global__ void __launch_bounds__(64) speaker_listener_step_kernel(SpeakerArgs a) {
+    const long long w = (long long)blockIdx.x * 64 + threadIdx.x;
+    const World& s = a.s;
+    if (w >= s.n) return;
+    constexpr int A = kSpkAgents, L = kSpkLandmarks;
+    double px[A], py[A], vx[A], vy[A], lx[L], ly[L];
+    load_world(s, w, A, L, px, py, vx, vy, lx, ly);
+    long long goal = a.goal[w];
+    // ---- the symbol becomes the communication state; only the listener takes a force and is integrated
+    long long comm = a.act[w * A + kSpeaker];
+    double fx[A] = {0.0, 0.0}, fy[A] = {0.0, 0.0};
+    action_force(a.act[w * A + kListener], fx[kListener], fy[kListener]);
+    integrate(A, px, py, vx, vy, fx, fy, kListener);
+    long long t = s.t[w] + 1;
+    // ---- reward (simple_speaker_listener.py:69-73): -|listener - goal landmark|^2 for both agents, shared as their sum
+    const double gx = goal == 0 ? lx[0] : goal == 1 ? lx[1] : lx[2];
+    const double gy = goal == 0 ? ly[0] : goal == 1 ? ly[1] : ly[2];
+    const double dx = px[kListener] - gx, dy = py[kListener] - gy;
+    double pa[A];
+    pa[0] = pa[1] = -(dx * dx + dy * dy);
+    const bool restart = write_outcome(s, w, A, t, pa, pa[0] + pa[1]);
+    if (restart) {
+        t = 0;
+        restart_from_fresh(s, w, A, L, 1.0, px, py, vx, vy, lx, ly);
+        goal = a.fresh_goal[w];
+        comm = -1;
+        a.goal[w] = goal;
+    }
+    store_world(s, w, A, L, t, restart, px, py, vx, vy, lx, ly);
+    a.comm[w] = comm;
+    // ---- observation of the (possibly restarted) world (simple_speaker_listener.py:75-98).  Speaker: the goal landmark's
+    // colour (palette: 0.65 on the landmark's own channel); listener: own velocity, landmarks relative to it, the
+    // speaker's communication state (one-hot)
+    float* o = s.obs + w * kSpkObs;
+    int k = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[k++] = goal == c ? 0.65f : 0.15f;
+    o[k++] = (float)vx[kListener];
+    o[k++] = (float)vy[kListener];
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+        o[k++] = (float)(lx[l] - px[kListener]);
+        o[k++] = (float)(ly[l] - py[kListener]);
+    }
+#pragma unroll
+    for (int sym = 0; sym < kSpkSymbols; ++sym) o[k++] = comm == sym ? 1.f : 0.f;
+}
+
 // one thread per world, 64 to a block
 template <typename ArgsT>
 int launch_step(void (*kernel)(ArgsT), const ArgsT& a, mappo_stream_t stream_) {
@@ -361,4 +426,19 @@ extern "C" int mappo_simple_reference_step(double* pos, double* vel, double* lan
                   n_worlds, world_length, auto_reset};
     return launch_step(reference_step_kernel, RefArgs{s, i64(goals), i64(comm), i64(actions), i64(fresh_goals)},
                        stream_);
+}
+
+extern "C" int mappo_simple_speaker_listener_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,
+                                                  int64_t* comm, const int64_t* actions, const double* fresh_pos,
+                                                  const double* fresh_landmarks, const int64_t* fresh_goal, float* obs,
+                                                  float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
+                                                  int world_length, int auto_reset, mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !goal || !comm || !actions || !obs || !rewards || !dones || !per_agent)
+        return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks || !fresh_goal)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || world_length < 1) return MAPPO_E_SHAPE;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    return launch_step(speaker_listener_step_kernel,
+                       SpeakerArgs{s, i64(goal), i64(comm), i64(actions), i64(fresh_goal)}, stream_);
 }

@@ -182,6 +182,7 @@ SIGNATURES = {
     "mappo_linear512_wgrad": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "mappo_simple_spread_step": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_reference_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
+    "mappo_simple_speaker_listener_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
     "mappo_abi_version": (_int, []),
     "mappo_build_info": (ctypes.c_char_p, []),
     "mappo_error_string": (ctypes.c_char_p, [_int]),

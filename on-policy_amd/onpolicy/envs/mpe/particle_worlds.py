@@ -1,7 +1,8 @@
 """What the multi-agent particle scenarios share: the physics constants (reference onpolicy/envs/mpe/core.py), the lazy
 ``infos`` of the device-resident envs, and ``TorchParticleWorlds``, the base class of worlds held as tensors on the
-policy's device.  A scenario (simple_spread.py, simple_reference.py) adds its spaces, its
-extra state, its forces, reward and observation, and the one native call that is its step on a HIP device.
+policy's device.  A scenario (simple_spread.py, simple_reference.py,
+simple_speaker_listener.py) adds its spaces, its extra state, its forces, reward and observation, and the one native call
+that is its step on a HIP device.
 """
 DT = 0.1
 DAMPING = 0.25
@@ -49,11 +50,14 @@ class TorchParticleWorlds(object):
     and consumes the same generator draws.
 
     A scenario supplies ``_fresh``, ``_forces``, ``_reward``, ``_obs``, ``_kernel_actions`` and ``_launch``; one with
-    state of its own extends ``state_names`` and ``_restart``."""
+    state of its own extends ``state_names`` and ``_restart``.  One whose agents observe vectors of different widths
+    passes the widths as a tuple for ``obs_dim`` (kept per agent in ``obs_dims``) and overrides ``_obs_shape``;
+    one with agents that do not move sets ``_movable``."""
     device_resident = True
     # the tensors a captured rollout graph snapshots / restores and expects to stay in place (runner/shared/rollout_graph.py)
     state_names = ("pos", "vel", "landmarks", "t")
     landmark_scale = 1.0        # restarted landmarks lie at landmark_scale * U(-1, 1)
+    _movable = None             # bool [1, A, 1] where some agents are not integrated (core.py:162); None: all move
 
     def __init__(self, n_threads, num_agents, num_landmarks, episode_length, seed, auto_reset, device, obs_dim,
                  action_space):
@@ -66,10 +70,14 @@ class TorchParticleWorlds(object):
         self.rng = torch.Generator(device=self.device)
         self.rng.manual_seed(int(seed))
         from onpolicy.envs.spaces import Box
-        self.obs_dim = obs_dim
-        self.observation_space = [Box(shape=(obs_dim,)) for _ in range(self.a)]
-        self.share_observation_space = [Box(shape=(obs_dim * self.a,)) for _ in range(self.a)]
-        self.action_space = [action_space() for _ in range(self.a)]
+        # observation width per agent; ``obs_dim`` only where all agents share one
+        dims = self.obs_dims = tuple(obs_dim) if isinstance(obs_dim, (tuple, list)) else (obs_dim,) * self.a
+        assert len(dims) == self.a, dims
+        if len(set(dims)) == 1:
+            self.obs_dim = dims[0]
+        self.observation_space = [Box(shape=(d,)) for d in dims]
+        self.share_observation_space = [Box(shape=(sum(dims),)) for _ in range(self.a)]
+        self.action_space = [action_space() for _ in range(self.a)] if callable(action_space) else list(action_space)
         f64 = dict(dtype=torch.float64, device=self.device)
         self.pos = torch.zeros(self.n, self.a, 2, **f64)
         self.vel = torch.zeros(self.n, self.a, 2, **f64)
@@ -111,12 +119,17 @@ class TorchParticleWorlds(object):
         actions = self._torch.as_tensor(actions, device=self.device)
         return self._step_kernel(actions) if self.graph_safe else self._step_ops(actions)
 
+    def _obs_shape(self):
+        """The shape observations leave ``step`` / ``reset`` in: [N, A, Do] where the agents share one width (a scenario
+        whose ``obs_dims`` differ has no ``obs_dim`` and lays its rows out itself)."""
+        return (self.n, self.a, self.obs_dim)
+
     def _step_kernel(self, actions):
         """The whole step as one launch: the arithmetic and the generator draws of ``_step_ops``."""
         torch = self._torch
         idx = self._kernel_actions(actions).to(torch.int64).contiguous()
         fresh = self._fresh() if self.auto_reset else None
-        obs = torch.empty(self.n, self.a, self.obs_dim, dtype=torch.float32, device=self.device)
+        obs = torch.empty(self._obs_shape(), dtype=torch.float32, device=self.device)
         rewards = torch.empty(self.n, self.a, 1, dtype=torch.float32, device=self.device)
         dones = torch.empty(self.n, self.a, dtype=torch.bool, device=self.device)
         per_agent = torch.empty(self.n, self.a, dtype=torch.float64, device=self.device)
@@ -129,8 +142,11 @@ class TorchParticleWorlds(object):
         torch = self._torch
         force = self._forces(actions)
         # core.py:160-175: damping, then force * dt; no mass / max speed in these scenarios
-        self.vel = self.vel * (1 - DAMPING) + force * DT
-        self.pos = self.pos + self.vel * DT
+        vel = self.vel * (1 - DAMPING) + force * DT
+        pos = self.pos + vel * DT
+        if self._movable is not None:
+            vel, pos = torch.where(self._movable, vel, self.vel), torch.where(self._movable, pos, self.pos)
+        self.vel, self.pos = vel, pos
         self.t = self.t + 1
         per_agent = self._reward()
         rewards = per_agent.sum(-1, keepdim=True).expand(self.n, self.a).unsqueeze(-1).to(torch.float32)

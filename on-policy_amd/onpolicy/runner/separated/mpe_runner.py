@@ -5,6 +5,12 @@ collect :94, insert :148, eval :179, render :237).
 As in the shared runner only the integer actions (device -> host) and the new observations / rewards /
 dones (host -> device) cross the PCIe bus per step; each agent's values, log-probs and RNN states go
 from its policy straight into its HBM buffer.
+
+With the worlds on the device (``envs.device_resident``: envs/mpe/simple_speaker_listener.py) nothing crosses it:
+``warmup`` / ``collect`` / ``insert`` work on tensors -- the env takes the policies' integer actions side by side and
+hands back one observation row per world, of which ``envs.agent_obs(obs, i)`` is agent i's view and the row itself the
+centralised critics' input -- and ``run`` replays the whole step from one captured graph where
+runner/separated/rollout_graph.py can build one.
 """
 import time
 
@@ -46,16 +52,27 @@ class MPERunner(Runner):
         start = time.time()
         episodes = int(self.num_env_steps) // self.episode_length // self.n_rollout_threads_job
         infos = []
+        # worlds on the device: the whole step (every agent's policy forward and sampling, env step, bookkeeping) as one
+        # captured graph launch + a slab write per agent (runner/separated/rollout_graph.py); None = the eager loop below
+        from onpolicy.runner.separated import rollout_graph
+        self.rollout_graph = rollout_graph.build(self) if episodes > 0 else None
         for episode in range(episodes):
             if self.use_linear_lr_decay:
                 for tr in self.trainer:
                     tr.policy.lr_decay(episode, episodes)
 
-            for step in range(self.episode_length):
-                values, actions, action_log_probs, rnn_states, rnn_states_critic, actions_env = self.collect(step)
-                obs, rewards, dones, infos = self.envs.step(actions_env)
-                self.insert((obs, rewards, dones, infos, values, actions, action_log_probs, rnn_states,
-                             rnn_states_critic))
+            if self.rollout_graph is not None:
+                for tr in self.trainer:
+                    tr.prep_rollout()
+                self.rollout_graph.begin_episode()
+                for step in range(self.episode_length):
+                    infos = self.rollout_graph.step()
+            else:
+                for step in range(self.episode_length):
+                    values, actions, action_log_probs, rnn_states, rnn_states_critic, actions_env = self.collect(step)
+                    obs, rewards, dones, infos = self.envs.step(actions_env)
+                    self.insert((obs, rewards, dones, infos, values, actions, action_log_probs, rnn_states,
+                                 rnn_states_critic))
 
             self.compute()
             train_infos = self.train()
@@ -84,8 +101,21 @@ class MPERunner(Runner):
     def _share_obs(self, obs, agent_id, joint):
         return joint if self.use_centralized_V else _agent_obs(obs, agent_id)
 
+    @property
+    def _on_device(self):
+        return getattr(self.envs, "device_resident", False)
+
+    def _device_insert_obs(self, obs, agent_id):
+        """-> (share_obs, obs) of one agent from the device worlds' observation rows."""
+        own = self.envs.agent_obs(obs, agent_id)
+        return (obs if self.use_centralized_V else own), own
+
     def warmup(self):
         obs = self.envs.reset()
+        if self._on_device:
+            for agent_id, b in enumerate(self.buffer):
+                b.share_obs[0], b.obs[0] = self._device_insert_obs(obs, agent_id)
+            return
         joint = _joint_obs(obs) if self.use_centralized_V else None
         for agent_id, b in enumerate(self.buffer):
             b.share_obs[0] = torch.as_tensor(self._share_obs(obs, agent_id, joint), dtype=torch.float32)
@@ -94,7 +124,7 @@ class MPERunner(Runner):
     @torch.no_grad()
     def collect(self, step):
         """-> per-agent lists of device tensors (values, actions, log-probs, RNN states) and the
-        [envs][agents] one-hot actions for the envs."""
+        [envs][agents] one-hot actions for the envs (device-resident worlds: the integer actions [N, A] as they are)."""
         values, actions, action_log_probs, rnn_states, rnn_states_critic, one_hot = [], [], [], [], [], []
         for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
             tr.prep_rollout()
@@ -105,11 +135,17 @@ class MPERunner(Runner):
             action_log_probs.append(action_log_prob)
             rnn_states.append(rnn_state)
             rnn_states_critic.append(rnn_state_critic)
-            one_hot.append(_one_hot(self.envs.action_space[agent_id], _t2n(action).astype(np.int64)))
-        actions_env = [[one_hot[a][i] for a in range(self.num_agents)] for i in range(self.n_rollout_threads)]
+            if not self._on_device:
+                one_hot.append(_one_hot(self.envs.action_space[agent_id], _t2n(action).astype(np.int64)))
+        if self._on_device:
+            actions_env = torch.cat(actions, -1)       # env state lives on the device: the indices never leave it
+        else:
+            actions_env = [[one_hot[a][i] for a in range(self.num_agents)] for i in range(self.n_rollout_threads)]
         return values, actions, action_log_probs, rnn_states, rnn_states_critic, actions_env
 
     def insert(self, data):
+        if self._on_device:
+            return self._insert_on_device(data)
         obs, rewards, dones, infos, values, actions, action_log_probs, rnn_states, rnn_states_critic = data
         dev = self.buffer[0].device
         alive = torch.as_tensor(~np.asarray(dones, dtype=bool), dtype=torch.float32, device=dev)   # [N, A]
@@ -122,6 +158,16 @@ class MPERunner(Runner):
                      rnn_states[agent_id] * keep.view(-1, 1, 1), rnn_states_critic[agent_id] * keep.view(-1, 1, 1),
                      actions[agent_id], action_log_probs[agent_id], values[agent_id], rewards[:, agent_id],
                      keep.view(-1, 1))
+
+    def _insert_on_device(self, data):
+        obs, rewards, dones, infos, values, actions, action_log_probs, rnn_states, rnn_states_critic = data
+        alive = torch.where(dones, 0.0, 1.0)                                                          # [N, A]
+        for agent_id, b in enumerate(self.buffer):
+            keep = alive[:, agent_id]
+            share, own = self._device_insert_obs(obs, agent_id)
+            b.insert(share, own, rnn_states[agent_id] * keep.view(-1, 1, 1),
+                     rnn_states_critic[agent_id] * keep.view(-1, 1, 1), actions[agent_id], action_log_probs[agent_id],
+                     values[agent_id], rewards[:, agent_id], keep.view(-1, 1))
 
     @torch.no_grad()
     def _act(self, envs, obs, rnn_states, masks):

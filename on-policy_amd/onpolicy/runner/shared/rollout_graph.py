@@ -29,11 +29,21 @@ from onpolicy.utils.graph_capture import capturing
 class RolloutGraph(object):
     WARMUP = 3
 
-    def __init__(self, runner):
+    def _init_common(self, runner, dev):
+        """What ``capture`` / ``step`` read whatever the carried state looks like (the separated graph starts here too)."""
         self.r = runner
-        b = runner.buffer
         self.N, self.A = runner.n_rollout_threads, runner.num_agents
+        self.dev = dev
+        self.popart = None
+        self.graph = None
+        self.out = None
+        self.infos = None
+        self.replays = 0
+
+    def __init__(self, runner):
+        b = runner.buffer
         dev = b.device
+        self._init_common(runner, dev)
         f32 = dict(dtype=torch.float32, device=dev)
         # carried state of the loop
         self.cur_obs = torch.empty(b.obs.shape[1:], **f32)
@@ -53,10 +63,6 @@ class RolloutGraph(object):
         if self.popart is not None:
             self.v_w = torch.empty_like(self.popart.weight.data)
             self.v_b = torch.empty_like(self.popart.bias.data)
-        self.graph = None
-        self.out = None
-        self.infos = None
-        self.replays = 0
 
     # -- the step itself: eager code, captured once
     @torch.no_grad()
@@ -99,7 +105,14 @@ class RolloutGraph(object):
     def _env_state(self):
         e = self.r.envs
         return {k: getattr(e, k).clone() for k in self._state_names()}, e.rng.get_state(), \
-            torch.cuda.get_rng_state(self.r.buffer.device)
+            torch.cuda.get_rng_state(self.dev)
+
+    def _carried(self):
+        """The static tensors that carry the loop's state from one replay to the next."""
+        return [self.cur_obs, self.cur_masks] + ([self.cur_rnn_a, self.cur_rnn_c] if self.recurrent else [])
+
+    def _prep_rollout(self):
+        self.r.trainer.prep_rollout()
 
     class _StaticHead(object):
         """While active, the PopArt head's parameters live in the graph's static tensors (same values)."""
@@ -126,17 +139,16 @@ class RolloutGraph(object):
         for k, v in state.items():
             getattr(e, k).copy_(v)
         e.rng.set_state(env_rng)
-        torch.cuda.set_rng_state(dev_rng, self.r.buffer.device)
+        torch.cuda.set_rng_state(dev_rng, self.dev)
 
     def capture(self):
         """Warm the step up on a side stream (library workspaces, lazy module state), capture it, and put worlds and
         generators back where they were: building the graph must not show in the trajectories."""
         r = self.r
-        dev = r.buffer.device
-        r.trainer.prep_rollout()
+        dev = self.dev
+        self._prep_rollout()
         self.begin_episode()
-        keep = (self.cur_obs.clone(), self.cur_masks.clone(),
-                self.cur_rnn_a.clone() if self.recurrent else None, self.cur_rnn_c.clone() if self.recurrent else None)
+        keep = [x.clone() for x in self._carried()]
         snap = self._env_state()
         state_ptrs = {k: getattr(r.envs, k).data_ptr() for k in self._state_names()}
         torch.cuda.synchronize(dev)
@@ -161,11 +173,8 @@ class RolloutGraph(object):
             self.graph = graph
         finally:
             self._restore(snap)
-            self.cur_obs.copy_(keep[0])
-            self.cur_masks.copy_(keep[1])
-            if self.recurrent:
-                self.cur_rnn_a.copy_(keep[2])
-                self.cur_rnn_c.copy_(keep[3])
+            for x, kept in zip(self._carried(), keep):
+                x.copy_(kept)
         return self
 
     def begin_episode(self):
@@ -189,26 +198,34 @@ class RolloutGraph(object):
         return self.infos.fresh()
 
 
-def build(runner):
-    """-> a captured RolloutGraph for ``runner``, or None when the step has to stay eager."""
+def capturable(envs, device):
+    """Whether a rollout step on ``envs`` with the buffers on ``device`` can be captured at all."""
     from onpolicy.algorithms.utils import distributions
     if os.environ.get("MAPPO_ROLLOUT_GRAPH", "1") == "0":
-        return None
-    envs = runner.envs
+        return False
     # device-resident worlds (envs/mpe/particle_worlds.py) declare ``graph_safe`` (the step advances the tensors named by
     # ``state_names`` in place: the K11 family does) and draw from their own generator ``rng``
     if not getattr(envs, "device_resident", False) or not envs.graph_safe:
-        return None
-    if torch.device(runner.buffer.device).type != "cuda" or distributions.SAMPLING_RNG != "device":
-        return None
-    if getattr(runner, "_mat", False):
-        return None
+        return False
+    return torch.device(device).type == "cuda" and distributions.SAMPLING_RNG == "device"
+
+
+def captured(make, device):
+    """``make().capture()``, or None where that fails: capture is an optimisation, anything it cannot take stays on the
+    eager loop."""
     try:
-        return RolloutGraph(runner).capture()
-    except Exception as exc:        # capture is an optimisation: anything it cannot take stays on the eager loop
+        return make().capture()
+    except Exception as exc:
         print("rollout graph: capture failed (%s: %s); the rollout stays eager" % (type(exc).__name__, exc))
         try:
-            torch.cuda.synchronize(runner.buffer.device)
+            torch.cuda.synchronize(device)
         except Exception:
             pass
         return None
+
+
+def build(runner):
+    """-> a captured RolloutGraph for ``runner``, or None when the step has to stay eager."""
+    if not capturable(runner.envs, runner.buffer.device) or getattr(runner, "_mat", False):
+        return None
+    return captured(lambda: RolloutGraph(runner), runner.buffer.device)

@@ -6,9 +6,10 @@ same algorithm-name -> recurrent-flag rewrite, same config dict handed to ``MPER
 Differences: simple_spread comes from the in-tree vectorised implementation (no gym / subprocess workers;
 ``--use_device_env`` keeps the training worlds on the GPU next to policy and buffer); with ``--use_device_env``
 simple_reference comes from the in-tree device implementation as well (envs/mpe/simple_reference.py, shared-policy
-runner only); every other case -- simple_reference without the flag, any other scenario, and the eval envs of
-``--use_eval`` in every case -- is built per worker from an external env tree (MAPPO_ENVS_PATH);
-wandb / setproctitle are optional.
+runner only), and so does simple_speaker_listener (envs/mpe/simple_speaker_listener.py: two agents with different
+spaces, so the separated runner only -- ``--share_policy`` -- with rmappo / mappo / ippo); every other case --
+simple_reference or simple_speaker_listener without the flag, any other scenario, and the eval envs of ``--use_eval``
+in every case -- is built per worker from an external env tree (MAPPO_ENVS_PATH); wandb / setproctitle are optional.
 Example (BASELINE.json configs[0]):
     python -m onpolicy.scripts.train.train_mpe --env_name MPE --scenario_name simple_spread \\
         --num_agents 3 --num_landmarks 3 --n_rollout_threads 8 --episode_length 25 \\
@@ -17,17 +18,26 @@ The reference's train_mpe_reference.sh on the device:
     python -m onpolicy.scripts.train.train_mpe --env_name MPE --algorithm_name rmappo --scenario_name simple_reference \
         --num_agents 2 --num_landmarks 3 --n_rollout_threads 128 --num_mini_batch 1 --episode_length 25 \
         --num_env_steps 3000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 --critic_lr 7e-4 --use_device_env
+The reference's train_mpe_comm.sh on the device (``--share_policy`` is a store_false flag: one policy per agent):
+    python -m onpolicy.scripts.train.train_mpe --env_name MPE --algorithm_name rmappo \
+        --scenario_name simple_speaker_listener --num_agents 2 --num_landmarks 3 --n_rollout_threads 128 \
+        --num_mini_batch 1 --episode_length 25 --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 \
+        --critic_lr 7e-4 --share_policy --use_device_env
 """
 import sys
 
 from onpolicy.config import get_config
 from onpolicy.envs.mpe.simple_reference import TorchSimpleReference
+from onpolicy.envs.mpe.simple_speaker_listener import TorchSimpleSpeakerListener
 from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread, VecSimpleSpread
 from onpolicy.scripts.train import _launch
 
 
 # scenarios with an in-tree device implementation (--use_device_env; row f1): the worlds are held on the policy's device
-DEVICE_ENVS = {"simple_spread": TorchSimpleSpread, "simple_reference": TorchSimpleReference}
+DEVICE_ENVS = {"simple_spread": TorchSimpleSpread, "simple_reference": TorchSimpleReference,
+               "simple_speaker_listener": TorchSimpleSpeakerListener}
+# ... of which these run under the separated runner (one policy per agent: the agents' spaces differ), the rest under the shared
+SEPARATED_DEVICE_ENVS = ("simple_speaker_listener",)
 
 
 def make_train_env(all_args, n_threads=None, seed_offset=0, device=None):
@@ -59,8 +69,9 @@ def parse_args(args, parser):
     parser.add_argument("--num_landmarks", type=int, default=3)
     parser.add_argument('--num_agents', type=int, default=2, help="number of players")
     parser.add_argument('--use_device_env', action='store_true', default=False,
-                        help="simple_spread or simple_reference with the training worlds held as tensors on the "
-                             "policy's device (shared-policy runner): no per-step host round trip")
+                        help="simple_spread or simple_reference (shared-policy runner) or simple_speaker_listener "
+                             "(separated runner) with the training worlds held as tensors on the policy's device: "
+                             "no per-step host round trip")
     return parser.parse_known_args(args)[0]
 
 
@@ -73,8 +84,14 @@ def main(args):
     run_dir = _launch.new_run_dir(all_args, all_args.scenario_name)
     _launch.seed_everything(all_args)
     shared = all_args.share_policy and all_args.algorithm_name not in ("happo", "hatrpo")
-    if all_args.use_device_env and not (shared and all_args.scenario_name in DEVICE_ENVS):
-        raise NotImplementedError("--use_device_env: %s with the shared-policy runner only" % " / ".join(DEVICE_ENVS))
+    if all_args.use_device_env:
+        scenario = all_args.scenario_name
+        separated = not shared and all_args.algorithm_name in ("rmappo", "mappo", "ippo")
+        if not (scenario in DEVICE_ENVS and (separated if scenario in SEPARATED_DEVICE_ENVS else shared)):
+            raise NotImplementedError(
+                "--use_device_env: %s with the shared-policy runner, %s with the separated runner (rmappo / mappo / ippo) "
+                "only" % (" / ".join(k for k in DEVICE_ENVS if k not in SEPARATED_DEVICE_ENVS),
+                          " / ".join(SEPARATED_DEVICE_ENVS)))
     envs = make_train_env(all_args, device=device if all_args.use_device_env else None)
     eval_envs = make_train_env(all_args, all_args.n_eval_rollout_threads, 50000) if all_args.use_eval else None
     if shared:
