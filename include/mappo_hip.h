@@ -386,6 +386,46 @@ typedef struct mappo_ppo_loss {
 } mappo_ppo_loss_t;
 int mappo_ppo_loss_f32(const mappo_ppo_loss_t* args, mappo_stream_t stream);
 
+/* ------------------------------------------------------ K7 for MultiDiscrete heads: one launch for all sub-heads ----
+ * The same loss for a MultiDiscrete action head (act.py, multi-discrete branch of evaluate_actions: one Categorical
+ * per sub-head, no availability mask; r_mappo.py:119-153).  logits [rows, S] holds the sub-heads' raw outputs side by
+ * side, S = sum of head_sizes; actions and old_logp are [rows, num_heads] (index as float; log-prob per sub-head).
+ * Per row and sub-head h: logp_h from the log-softmax of the head's logits, ratio_h = exp(logp_h - old_logp_h),
+ * surr_h = min(ratio_h * adv, clamp(ratio_h, 1 -+ clip) * adv).  The row's policy term is -sum_h surr_h; the entropy is
+ * the mean over sub-heads of the per-head (masked) means, so the row's entropy term is sum_h H_h / num_heads.
+ * adv, active (NULL = 1), values, value_preds, returns [rows], norm, inv_denoms, the scalars and the flags are those of
+ * mappo_ppo_loss_f32; the value half is the same arithmetic.  Everything but active and norm is required.
+ * Outputs: dlogits [rows, S] = d(policy_loss - entropy_coef * entropy) / dlogits, dvalues [rows],
+ *          sums[4] += { sum w_p * (-sum_h surr_h), sum w_p * sum_h H_h / num_heads, sum w_v * value_loss,
+ *                       sum (sum_h ratio_h / num_heads) }  (float64, atomically accumulated).
+ * 1 <= num_heads <= MAPPO_LOSS_MULTI_MAX_HEADS, every head_sizes[h] >= 1, S <= 64 (the limits of
+ * mappo_multi_categorical_sample); MAPPO_E_SHAPE otherwise. */
+#define MAPPO_LOSS_MULTI_MAX_HEADS 8
+typedef struct mappo_ppo_loss_multi {
+    const float* logits;
+    const float* actions;
+    const float* old_logp;
+    const float* adv;
+    const float* active;
+    const float* values;
+    const float* value_preds;
+    const float* returns;
+    const float* norm;
+    const float* inv_denoms;
+    float* dlogits;
+    float* dvalues;
+    double* sums;
+    int64_t rows;
+    int num_heads;
+    int head_sizes[MAPPO_LOSS_MULTI_MAX_HEADS];
+    float clip;
+    float huber_delta;
+    float entropy_coef;
+    float value_loss_coef;
+    unsigned flags;
+} mappo_ppo_loss_multi_t;
+int mappo_ppo_loss_multi_f32(const mappo_ppo_loss_multi_t* args, mappo_stream_t stream);
+
 /* ------------------------------------------------------------------ K14: categorical sampling for the rollout ----
  * Replaces, for one Discrete head and one draw per row, Categorical.forward's availability masking
  * (onpolicy/algorithms/utils/distributions.py:64-67), FixedCategorical.sample (:15-16) and .log_probs (:18-25) as

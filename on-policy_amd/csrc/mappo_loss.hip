@@ -36,6 +36,49 @@ __device__ __forceinline__ float dloss_of(float e, float delta, bool huber) {
     return ae <= delta ? e : (e > 0.f ? delta : -delta);
 }
 
+// The clipped value loss of one row (r_mappo.py:52-89) and, in *grad, its derivative w.r.t. the value.
+__device__ __forceinline__ float value_loss_of(float v, float vp, float target, float clip, float delta, bool huber,
+                                               bool clipped_value, float* grad) {
+    const float d = v - vp;
+    const float vpc = vp + fminf(fmaxf(d, -clip), clip);  // r_mappo.py:62-63
+    const float e_c = target - vpc, e_o = target - v;
+    const float l_c = loss_of(e_c, delta, huber), l_o = loss_of(e_o, delta, huber);
+    const float g_o = -dloss_of(e_o, delta, huber);
+    const float g_c = (d >= -clip && d <= clip) ? -dloss_of(e_c, delta, huber) : 0.f;
+    float vl = l_o, g = g_o;
+    if (clipped_value) {  // torch.max: the larger branch, both halves on a tie
+        if (l_c > l_o) {
+            vl = l_c;
+            g = g_c;
+        } else if (l_c == l_o) {
+            g = 0.5f * (g_o + g_c);
+        }
+    }
+    *grad = g;
+    return vl;
+}
+
+// A workgroup's four float64 sums: per wave, per workgroup of four waves, then one atomic each (sums may be NULL).
+__device__ __forceinline__ void add_sums(double s_policy, double s_entropy, double s_value, double s_ratio, double* sums) {
+    __shared__ double red[4][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    s_policy = wave_sum_d(s_policy);
+    s_entropy = wave_sum_d(s_entropy);
+    s_value = wave_sum_d(s_value);
+    s_ratio = wave_sum_d(s_ratio);
+    if (lane == 0) {
+        red[wave][0] = s_policy;
+        red[wave][1] = s_entropy;
+        red[wave][2] = s_value;
+        red[wave][3] = s_ratio;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && sums != nullptr) {
+        double t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        atomicAdd(sums + threadIdx.x, t);
+    }
+}
+
 // STAGED: the [256, n_actions] logits / availability tile of a workgroup goes through LDS with coalesced
 // global accesses (a thread's own row is n_actions floats at a stride of n_actions: 20-byte pieces for the
 // 5 actions of MPE), and the gradient tile goes back the same way.  Rows sit at an odd word stride in LDS.
@@ -198,46 +241,130 @@ __global__ void __launch_bounds__(256) ppo_loss_kernel(mappo_ppo_loss_t a) {
         if (STAGED && a.logits != nullptr) __syncthreads();   // the tile is free for the next iteration
         // ---------------- critic: clipped value loss against the (normalised) return
         if (live && a.values != nullptr) {
-            const float v = a.values[i], vp = a.value_preds[i];
             const float target = a.norm != nullptr ? (a.returns[i] - nmean) / nstd : a.returns[i];
-            const float d = v - vp;
-            const float vpc = vp + fminf(fmaxf(d, -a.clip), a.clip);  // r_mappo.py:62-63
-            const float e_c = target - vpc, e_o = target - v;
-            const float l_c = loss_of(e_c, a.huber_delta, huber), l_o = loss_of(e_o, a.huber_delta, huber);
-            const float g_o = -dloss_of(e_o, a.huber_delta, huber);
-            const float g_c = (d >= -a.clip && d <= a.clip) ? -dloss_of(e_c, a.huber_delta, huber) : 0.f;
-            float vl = l_o, g = g_o;
-            if (clipped_value) {  // torch.max: the larger branch, both halves on a tie
-                if (l_c > l_o) {
-                    vl = l_c;
-                    g = g_c;
-                } else if (l_c == l_o) {
-                    g = 0.5f * (g_o + g_c);
-                }
-            }
+            float g;
+            const float vl = value_loss_of(a.values[i], a.value_preds[i], target, a.clip, a.huber_delta, huber, clipped_value, &g);
             const float wv = v_active ? am : 1.f;
             s_value += (double)(vl * wv);
             if (a.dvalues != nullptr) a.dvalues[i] = a.value_loss_coef * g * wv * inv_dv;
         }
     }
 
-    __shared__ double red[4][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    s_policy = wave_sum_d(s_policy);
-    s_entropy = wave_sum_d(s_entropy);
-    s_value = wave_sum_d(s_value);
-    s_ratio = wave_sum_d(s_ratio);
-    if (lane == 0) {
-        red[wave][0] = s_policy;
-        red[wave][1] = s_entropy;
-        red[wave][2] = s_value;
-        red[wave][3] = s_ratio;
+    add_sums(s_policy, s_entropy, s_value, s_ratio, a.sums);
+}
+
+// K7 for a MultiDiscrete head (act.py, multi-discrete branch of evaluate_actions: one Categorical per sub-head, no
+// availability mask).  The sub-heads' logits lie side by side in a row of `width` floats; the [256, width] tile is staged
+// as in ppo_loss_kernel and a thread walks its row head by head: log-softmax, entropy and clipped surrogate of the head,
+// then the head's gradient over its own logits, in place.  The row's policy term is the sum over heads, its entropy and
+// its ratio the mean over heads (the reference's sum(ents) / len(ents) and imp_weights.mean() over [rows, heads]).
+// The head sizes come with the arguments: wave-uniform.
+__global__ void __launch_bounds__(256) ppo_multi_loss_kernel(mappo_ppo_loss_multi_t a, int width) {
+    extern __shared__ float lds[];
+    const bool huber = a.flags & MAPPO_LOSS_HUBER;
+    const bool clipped_value = a.flags & MAPPO_LOSS_CLIPPED_VALUE;
+    const bool p_active = a.flags & MAPPO_LOSS_POLICY_ACTIVE_MASKS;
+    const bool v_active = a.flags & MAPPO_LOSS_VALUE_ACTIVE_MASKS;
+    const int nh = a.num_heads;
+    const float inv_dp = a.inv_denoms[0], inv_dv = a.inv_denoms[1];
+    float nmean = 0.f, nstd = 1.f;
+    if (a.norm != nullptr) {  // {sigma, mu}
+        nstd = a.norm[0];
+        nmean = a.norm[1];
     }
-    __syncthreads();
-    if (threadIdx.x < 4 && a.sums != nullptr) {
-        double t = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        atomicAdd(a.sums + threadIdx.x, t);
+    const float ent_coef = a.entropy_coef / (float)nh;      // of one head's entropy in the mean over heads
+    const double inv_heads = 1.0 / (double)nh;
+    const float lo = 1.f - a.clip, hi = 1.f + a.clip;
+    double s_policy = 0.0, s_entropy = 0.0, s_value = 0.0, s_ratio = 0.0;
+    const int stride = width | 1;
+    // element e = threadIdx.x + 256 j of the staged tile is (row, column) = (e / width, e % width): stepped, not divided
+    const int r0 = threadIdx.x / width, k0 = threadIdx.x - r0 * width, dr = 256 / width, dk = 256 - dr * width;
+
+    for (long long base = (long long)blockIdx.x * 256; base < a.rows; base += (long long)gridDim.x * 256) {
+        const long long i = base + threadIdx.x;
+        const bool live = i < a.rows;
+        const long long left = a.rows - base;
+        const int tile = (int)(left < 256 ? left : 256) * width;
+        const float* gl = a.logits + base * width;
+        for (int e = threadIdx.x, r = r0, k = k0; e < tile; e += 256) {
+            lds[r * stride + k] = gl[e];
+            r += dr;
+            k += dk;
+            if (k >= width) {
+                k -= width;
+                ++r;
+            }
+        }
+        __syncthreads();
+        const float am = (live && a.active != nullptr) ? a.active[i] : 1.f;
+        if (live) {
+            const float adv = a.adv[i];
+            const float wp = p_active ? am : 1.f;
+            const float scale = wp * inv_dp;
+            double surr_row = 0.0, ent_row = 0.0, ratio_row = 0.0;
+            float* lg = lds + threadIdx.x * stride;         // this head's logits, then its gradient
+            for (int h = 0; h < nh; ++h) {
+                const int na = a.head_sizes[h];
+                const int act = (int)a.actions[i * nh + h];
+                float mx = -INFINITY;
+                for (int k = 0; k < na; ++k) mx = fmaxf(mx, lg[k]);
+                float se = 0.f;
+                for (int k = 0; k < na; ++k) se += expf(lg[k] - mx);
+                const float lse = mx + logf(se);
+                float ent = 0.f, logp_a = 0.f;
+                for (int k = 0; k < na; ++k) {
+                    const float lp = lg[k] - lse;
+                    ent -= expf(lp) * lp;
+                    if (k == act) logp_a = lp;
+                }
+                const float ratio = expf(logp_a - a.old_logp[i * nh + h]);  // r_mappo.py:129
+                const float surr1 = ratio * adv;
+                // (comparisons, not fminf / fmaxf: a NaN ratio is handed on, as in ppo_loss_kernel)
+                const float rc = ratio < lo ? lo : (ratio > hi ? hi : ratio);
+                const float surr2 = rc * adv;
+                const float s = (surr1 < surr2 || surr1 != surr1) ? surr1 : surr2;
+                const bool inside = ratio >= lo && ratio <= hi;
+                const float ds_dratio = (inside || surr1 < surr2) ? adv : 0.f;  // min / clamp sub-gradients as autograd takes them
+                surr_row += (double)s;
+                ent_row += (double)ent;
+                ratio_row += (double)ratio;
+                // d/dl_j of [ -s_h - c_ent / heads * H_h ] * wp / D_p, as in ppo_loss_kernel
+                const float g_logp = -ds_dratio * ratio;
+                for (int k = 0; k < na; ++k) {
+                    const float lp = lg[k] - lse;
+                    const float p = expf(lp);
+                    const float g = g_logp * ((k == act ? 1.f : 0.f) - p) + ent_coef * p * (lp + ent);
+                    lg[k] = g * scale;
+                }
+                lg += na;
+            }
+            s_policy += -surr_row * (double)wp;
+            s_entropy += ent_row * inv_heads * (double)wp;
+            s_ratio += ratio_row * inv_heads;
+        }
+        __syncthreads();
+        float* gd = a.dlogits + base * width;
+        for (int e = threadIdx.x, r = r0, k = k0; e < tile; e += 256) {
+            gd[e] = lds[r * stride + k];
+            r += dr;
+            k += dk;
+            if (k >= width) {
+                k -= width;
+                ++r;
+            }
+        }
+        __syncthreads();   // the tile is free for the next iteration
+        if (live) {
+            const float target = a.norm != nullptr ? (a.returns[i] - nmean) / nstd : a.returns[i];
+            float g;
+            const float vl = value_loss_of(a.values[i], a.value_preds[i], target, a.clip, a.huber_delta, huber, clipped_value, &g);
+            const float wv = v_active ? am : 1.f;
+            s_value += (double)(vl * wv);
+            a.dvalues[i] = a.value_loss_coef * g * wv * inv_dv;
+        }
     }
+
+    add_sums(s_policy, s_entropy, s_value, s_ratio, a.sums);
 }
 
 }  // namespace
@@ -277,6 +404,31 @@ extern "C" int mappo_ppo_loss_f32(const mappo_ppo_loss_t* args, mappo_stream_t s
         if (avail) hipLaunchKernelGGL((ppo_loss_kernel<true, false, 0>), grid, block, 0, stream, a);
         else hipLaunchKernelGGL((ppo_loss_kernel<false, false, 0>), grid, block, 0, stream, a);
     }
+    return (int)hipGetLastError();
+}
+
+extern "C" int mappo_ppo_loss_multi_f32(const mappo_ppo_loss_multi_t* args, mappo_stream_t stream_) {
+    if (!args) return MAPPO_E_NULL;
+    mappo_ppo_loss_multi_t a = *args;
+    if (!a.logits || !a.actions || !a.old_logp || !a.adv || !a.values || !a.value_preds || !a.returns || !a.inv_denoms ||
+        !a.dlogits || !a.dvalues || !a.sums)
+        return MAPPO_E_NULL;
+    if (a.rows <= 0 || a.num_heads <= 0 || a.num_heads > MAPPO_LOSS_MULTI_MAX_HEADS) return MAPPO_E_SHAPE;
+    int width = 0;
+    for (int h = 0; h < a.num_heads; ++h) {
+        if (a.head_sizes[h] <= 0 || a.head_sizes[h] > 64) return MAPPO_E_SHAPE;
+        width += a.head_sizes[h];
+    }
+    if (width > 64) return MAPPO_E_SHAPE;
+    if (a.flags & ~15u) return MAPPO_E_FLAGS;
+    long long blocks = (a.rows + 255) / 256;
+    if (blocks > mappo::kCUs * 8) blocks = mappo::kCUs * 8;
+    // the [256, width | 1] tile: 66,560 B at 64 logits, above what a kernel gets without being granted it
+    const size_t lds = (size_t)256 * (width | 1) * sizeof(float);
+    hipError_t e = mappo::grant_lds(&ppo_multi_loss_kernel, lds);   // once per (device, kernel), not per launch
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(ppo_multi_loss_kernel, dim3((unsigned)blocks), dim3(256), lds, static_cast<hipStream_t>(stream_), a,
+                       width);
     return (int)hipGetLastError();
 }
 

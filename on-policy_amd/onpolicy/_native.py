@@ -76,6 +76,18 @@ class PPOLoss(ctypes.Structure):
                 ("value_loss_coef", ctypes.c_float), ("flags", ctypes.c_uint)]
 
 
+LOSS_MULTI_MAX_HEADS = 8    # MAPPO_LOSS_MULTI_MAX_HEADS
+
+
+class PPOLossMulti(ctypes.Structure):
+    """struct mappo_ppo_loss_multi (include/mappo_hip.h)."""
+    _fields_ = [(n, _vp) for n in ("logits", "actions", "old_logp", "adv", "active", "values", "value_preds", "returns",
+                                   "norm", "inv_denoms", "dlogits", "dvalues", "sums")] + \
+               [("rows", _i64), ("num_heads", ctypes.c_int), ("head_sizes", ctypes.c_int * LOSS_MULTI_MAX_HEADS),
+                ("clip", ctypes.c_float), ("huber_delta", ctypes.c_float), ("entropy_coef", ctypes.c_float),
+                ("value_loss_coef", ctypes.c_float), ("flags", ctypes.c_uint)]
+
+
 class MLP(ctypes.Structure):
     """struct mappo_mlp (include/mappo_hip.h): the fused hidden-64 trunk."""
     _fields_ = [("src", _vp), ("row_tab", _vp), ("rows", _i64),
@@ -158,6 +170,7 @@ SIGNATURES = {
     "mappo_adam_workspace_floats": (_i64, []),
     "mappo_clip_adam": (_int, [ctypes.POINTER(Adam), _vp]),
     "mappo_ppo_loss_f32": (_int, [ctypes.POINTER(PPOLoss), _vp]),
+    "mappo_ppo_loss_multi_f32": (_int, [ctypes.POINTER(PPOLossMulti), _vp]),
     "mappo_categorical_sample": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
     "mappo_multi_categorical_sample": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _i64, _vp]),
     "mappo_minibatch_workspace_ints": (_i64, [_i64, _int]),

@@ -71,7 +71,8 @@ class R_MAPPOPolicy:
 
     def evaluate_logits(self, cent_obs, obs, rnn_states_actor, rnn_states_critic, masks, obs_standardized=False,
                         need_actor=True):
-        """-> (values, logits of the Discrete action head or None): the inputs of the fused PPO loss.
+        """-> (values, logits of the Discrete action head -- of all sub-heads of a MultiDiscrete one, side by side -- or
+        None): the inputs of the fused PPO loss.
 
         Evaluations of at most MAPPO_TWO_STREAM_MAX_ROWS rows (default 2^20: the minibatches whose ``ppo_update`` is replayed
         from a HIP graph, update_graph.py, and the row spans a larger hidden-512 minibatch is cut into) run the critic on a

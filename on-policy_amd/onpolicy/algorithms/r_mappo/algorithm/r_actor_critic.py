@@ -94,8 +94,12 @@ class R_Actor(nn.Module, _DeviceMixin):
 
 
     def evaluate_logits(self, obs, rnn_states, masks, obs_standardized=False):
-        """Raw outputs of the Discrete action head for the fused PPO loss (K7), [B, n_actions]."""
+        """Raw outputs of the action head for the fused PPO loss (K7): [B, n_actions] of a Discrete head, the sub-heads'
+        outputs side by side, [B, sum head_sizes], of a MultiDiscrete one (trunk and GRU as everywhere else; the head is
+        not folded into their kernels)."""
         obs, rnn_states, masks = self._to_device(obs, rnn_states, masks)
+        if self.act.multi_discrete:
+            return self.act.multi_logits(self._features(obs, rnn_states, masks, obs_standardized)[0])
         head = self.act.action_out.linear
         if self._fuses_head(obs, head):
             return self.base(obs, head=head)          # gather + trunk + head: one launch

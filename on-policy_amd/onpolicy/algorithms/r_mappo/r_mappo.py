@@ -114,8 +114,10 @@ class R_MAPPO():
         self._obs_standardized = False
         # ppo_update as a captured HIP graph (update_graph.py), built on first use
         self._update_graph = None
-        # Discrete head on a HIP device: loss + gradient in one kernel (K7) instead of the framework ops
-        self._fused_loss = fused_loss.supported(self.policy, device) and self._fused_loss_allowed()
+        # Discrete head on a HIP device: loss + gradient in one kernel (K7) instead of the framework ops.  A MultiDiscrete
+        # head only where asked for, and only in R_MAPPO itself: HAPPO's ratio is a product over the sub-heads.
+        multi = type(self) is R_MAPPO and fused_loss.multi_enabled(args)
+        self._fused_loss = fused_loss.supported(self.policy, device, multi=multi) and self._fused_loss_allowed()
 
     # ------------------------------------------------------------------ what HAPPO overrides
     _use_factor = False          # minibatches may carry a 13th element (HAPPO factor); MAPPO ignores it
@@ -372,13 +374,19 @@ class R_MAPPO():
         self._feed_normalizer(pro)
         normalized = self._use_popart or self._use_valuenorm
         norm = self.value_normalizer.denorm_scalars().to(values.device, torch.float32).contiguous() if normalized else None
-        dlogits, dvalues = fused_loss.ppo_loss(
-            logits, mb.available_actions, mb.actions, mb.old_action_log_probs, mb.adv_targ, mb.active_masks, mb.factor,
-            values, mb.value_preds, mb.returns, norm, pro.inv, pro.sums,
-            clip=self.clip_param, huber_delta=self.huber_delta, entropy_coef=self.entropy_coef,
-            value_loss_coef=self.value_loss_coef, use_huber=self._use_huber_loss,
-            use_clipped_value_loss=self._use_clipped_value_loss,
-            policy_active_masks=self._use_policy_active_masks, value_active_masks=self._use_value_active_masks)
+        hyper = dict(clip=self.clip_param, huber_delta=self.huber_delta, entropy_coef=self.entropy_coef,
+                     value_loss_coef=self.value_loss_coef, use_huber=self._use_huber_loss,
+                     use_clipped_value_loss=self._use_clipped_value_loss,
+                     policy_active_masks=self._use_policy_active_masks, value_active_masks=self._use_value_active_masks)
+        act = self.policy.actor.act
+        if act.multi_discrete:      # all sub-heads in one launch (mappo_ppo_loss_multi_f32); no mask, no factor for this head
+            dlogits, dvalues = fused_loss.ppo_loss_multi(
+                logits, act.head_sizes, mb.actions, mb.old_action_log_probs, mb.adv_targ, mb.active_masks,
+                values, mb.value_preds, mb.returns, norm, pro.inv, pro.sums, **hyper)
+        else:
+            dlogits, dvalues = fused_loss.ppo_loss(
+                logits, mb.available_actions, mb.actions, mb.old_action_log_probs, mb.adv_targ, mb.active_masks, mb.factor,
+                values, mb.value_preds, mb.returns, norm, pro.inv, pro.sums, **hyper)
         if update_actor:
             torch.autograd.backward([logits, values], [dlogits, dvalues])
         else:

@@ -51,10 +51,8 @@ class ACTLayer(nn.Module):
         if self.multi_discrete and not deterministic:
             from . import fused_loss
             if fused_loss.multi_sample_supported(x, self.head_sizes):
-                # K14 for all sub-heads in one launch; the sub-heads' Linears stay separate modules (checkpoint keys
-                # action_outs.{k}.linear.*), their logits side by side
-                logits = torch.cat([head.linear(x) for head in self.action_outs], -1)
-                return fused_loss.sample_multi_categorical(logits, self.head_sizes)
+                # K14 for all sub-heads in one launch
+                return fused_loss.sample_multi_categorical(self.multi_logits(x), self.head_sizes)
         if self.mixed_action or self.multi_discrete:
             actions, log_probs = [], []
             for head in self.action_outs:
@@ -72,6 +70,11 @@ class ACTLayer(nn.Module):
         dist = self._single(x, available_actions)
         actions = dist.mode() if deterministic else dist.sample()
         return actions, dist.log_probs(actions)
+
+    def multi_logits(self, x):
+        """The MultiDiscrete sub-heads' raw outputs side by side, [B, sum head_sizes] (what the one-launch sampler and the
+        fused loss read); the sub-heads' Linears stay separate modules (checkpoint keys action_outs.{k}.linear.*)."""
+        return torch.cat([head.linear(x) for head in self.action_outs], -1)
 
     def from_logits(self, logits, available_actions=None, deterministic=False):
         """``forward`` for a Discrete head whose Linear was already evaluated (inside the fused trunk launch): masking,

@@ -4,24 +4,41 @@ Discrete action head in one pass over a minibatch span, instead of ~100 elementw
 ``torch.autograd.backward`` at the head's logits and the critic's values.
 
 Used when the policy has a single Categorical head and the tensors are on a HIP device; everything else
-(MultiDiscrete / continuous / mixed heads, CPU) takes the framework path in ``R_MAPPO.ppo_update``.
-``MAPPO_FUSED_LOSS=0`` disables it.
+(continuous / mixed heads, CPU) takes the framework path in ``R_MAPPO.ppo_update``.  A MultiDiscrete head has its own
+kernel (``mappo_ppo_loss_multi_f32``, all sub-heads in one launch), which ``R_MAPPO`` itself uses when asked to
+(``MAPPO_FUSED_LOSS_MULTI=1`` or train_mpe.py's ``--fused_multi_loss``; the framework path otherwise).
+``MAPPO_FUSED_LOSS=0`` disables both.
 """
+import ctypes
 import os
 
 import torch
 
 from onpolicy import _native
 
+LOSS_MULTI_MAX_HEADS = _native.LOSS_MULTI_MAX_HEADS
+
 
 def enabled():
     return os.environ.get("MAPPO_FUSED_LOSS", "1") != "0"
 
 
-def supported(policy, device):
+def multi_enabled(args=None):
+    """The MultiDiscrete form of K7 is opt-in: ``MAPPO_FUSED_LOSS_MULTI=1`` or train_mpe.py's ``--fused_multi_loss``."""
+    return os.environ.get("MAPPO_FUSED_LOSS_MULTI", "0") == "1" or bool(getattr(args, "fused_multi_loss", False))
+
+
+def supported(policy, device, multi=False):
+    """The fused loss takes this policy on this device: a Discrete head, or -- with ``multi`` -- a MultiDiscrete head within
+    the limits of ``mappo_ppo_loss_multi_f32``."""
     act = getattr(getattr(policy, "actor", None), "act", None)
-    return (enabled() and torch.device(device).type == "cuda" and act is not None
-            and getattr(act, "action_type", None) == "Discrete" and hasattr(policy, "evaluate_logits"))
+    if not (enabled() and torch.device(device).type == "cuda" and act is not None and hasattr(policy, "evaluate_logits")):
+        return False
+    kind = getattr(act, "action_type", None)
+    if kind == "MultiDiscrete":
+        sizes = act.head_sizes
+        return multi and 0 < len(sizes) <= LOSS_MULTI_MAX_HEADS and min(sizes) >= 1 and sum(sizes) <= 64
+    return kind == "Discrete"
 
 
 def _flat(x):
@@ -49,6 +66,33 @@ def ppo_loss(logits, available_actions, actions, old_logp, adv, active, factor, 
                         | (_native.LOSS_POLICY_ACTIVE_MASKS if policy_active_masks else 0)
                         | (_native.LOSS_VALUE_ACTIVE_MASKS if value_active_masks else 0))
     _native.check(_native.lib().mappo_ppo_loss_f32(a, _native.stream_of(lg.device)), "mappo_ppo_loss_f32")
+    return dlogits, dvalues.view_as(values)
+
+
+def ppo_loss_multi(logits, head_sizes, actions, old_logp, adv, active, values, value_preds, returns, norm, inv_denoms,
+                   sums, *, clip, huber_delta, entropy_coef, value_loss_coef, use_huber, use_clipped_value_loss,
+                   policy_active_masks, value_active_masks):
+    """K7 for a MultiDiscrete head (``mappo_ppo_loss_multi_f32``) -> (dlogits, dvalues).  ``logits`` [rows, sum head_sizes]
+    holds the sub-heads' logits side by side, ``actions`` / ``old_logp`` are [rows, len(head_sizes)].  ``sums`` accumulates
+    {sum w_p * (-sum_h surrogate_h), sum w_p * mean_h entropy_h, sum w_v * value_loss, sum mean_h ratio_h}."""
+    rows, width = logits.shape
+    k = len(head_sizes)
+    assert width == sum(head_sizes) and tuple(actions.shape) == (rows, k) and tuple(old_logp.shape) == (rows, k)
+    lg = logits.detach().contiguous()
+    dlogits = torch.empty_like(lg)
+    v = _flat(values)
+    dvalues = torch.empty_like(v)
+    keep = [lg, _flat(actions), _flat(old_logp), _flat(adv), _flat(active), v, _flat(value_preds), _flat(returns), norm,
+            inv_denoms]
+    p = _native.ptr
+    sizes = (ctypes.c_int * LOSS_MULTI_MAX_HEADS)(*[int(n) for n in head_sizes])
+    a = _native.PPOLossMulti(*[p(t) for t in keep], p(dlogits), p(dvalues), p(sums), rows, k, sizes, float(clip),
+                             float(huber_delta), float(entropy_coef), float(value_loss_coef),
+                             (_native.LOSS_HUBER if use_huber else 0)
+                             | (_native.LOSS_CLIPPED_VALUE if use_clipped_value_loss else 0)
+                             | (_native.LOSS_POLICY_ACTIVE_MASKS if policy_active_masks else 0)
+                             | (_native.LOSS_VALUE_ACTIVE_MASKS if value_active_masks else 0))
+    _native.check(_native.lib().mappo_ppo_loss_multi_f32(a, _native.stream_of(lg.device)), "mappo_ppo_loss_multi_f32")
     return dlogits, dvalues.view_as(values)
 
 
@@ -94,7 +138,6 @@ def sample_multi_categorical(logits, head_sizes):
     by side in ``logits`` [rows, sum head_sizes] (``mappo_multi_categorical_sample``): what ACTLayer.forward's
     multi-discrete branch gives with one FixedCategorical per sub-head.  The Exponential(1) noise is drawn per sub-head in
     head order, as the framework's per-head torch.multinomial(p, 1) draws it, so both paths consume the same stream."""
-    import ctypes
     rows = logits.shape[0]
     k = len(head_sizes)
     lg = logits.detach().contiguous()

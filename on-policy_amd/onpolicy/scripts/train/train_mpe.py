@@ -24,6 +24,7 @@ The reference's train_mpe_comm.sh on the device (``--share_policy`` is a store_f
         --num_mini_batch 1 --episode_length 25 --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 \
         --critic_lr 7e-4 --share_policy --use_device_env
 """
+import argparse
 import sys
 
 from onpolicy.config import get_config
@@ -72,6 +73,12 @@ def parse_args(args, parser):
                         help="simple_spread or simple_reference (shared-policy runner) or simple_speaker_listener "
                              "(separated runner) with the training worlds held as tensors on the policy's device: "
                              "no per-step host round trip")
+    # (argparse.SUPPRESS: the attribute exists only when the flag is given, so a default parse carries the reference's flags
+    # and --use_device_env, nothing else; readers use getattr(args, "fused_multi_loss", False))
+    parser.add_argument('--fused_multi_loss', action='store_true', default=argparse.SUPPRESS,
+                        help="rmappo / mappo / ippo with a MultiDiscrete action head (simple_reference) on a HIP device: "
+                             "the PPO loss of all sub-heads as one kernel launch and the update as a captured graph "
+                             "(MAPPO_FUSED_LOSS_MULTI=1 does the same)")
     return parser.parse_known_args(args)[0]
 
 
