@@ -449,6 +449,28 @@ int mappo_multi_categorical_sample(const float* logits, const float* const* nois
                                    int num_heads, int64_t* actions, float* log_probs, int64_t rows,
                                    mappo_stream_t stream);
 
+/* ------------------------------------------------- K14 mode: the deterministic action of a Categorical head ----
+ * Replaces, for one Discrete head, Categorical.forward's availability masking
+ * (onpolicy/algorithms/utils/distributions.py:64-67), FixedCategorical.mode (:27-28) and .log_probs (:18-25) as called
+ * by ACTLayer.forward with deterministic=True (onpolicy/algorithms/utils/act.py:55-60):
+ *   x_i = available_i == 0 ? -1e10 : logits_i;  action = the LOWEST i at which x_i is maximal (compared as float32:
+ *   softmax is monotone, so this is the mode);  log_probs = x[action] - logsumexp(x), evaluated as
+ *   -log(sum_i exp(x_i - x[action])): no rounding at the size of the logits.
+ *   logits [rows, n_actions] (finite values only: a NaN or an infinity is outside the contract), available
+ *   [rows, n_actions] or NULL, actions [rows] int64, log_probs [rows]; n_actions <= 64.
+ * MAPPO_E_NULL / MAPPO_E_SHAPE are returned before anything touches the device. */
+int mappo_categorical_mode(const float* logits, const float* available, int64_t* actions, float* log_probs,
+                           int64_t rows, int n_actions, mappo_stream_t stream);
+
+/* --------------------------------------------- K14 mode for MultiDiscrete heads: one launch for all sub-heads ----
+ * ACTLayer.forward's multi-discrete branch with deterministic=True (onpolicy/algorithms/utils/act.py:44-60: per
+ * sub-head FixedCategorical.mode / log_probs, distributions.py:14-28, then cat), no availability mask.
+ * logits [rows, sum_k head_sizes[k]] (finite), head_sizes: host array.  Outputs actions [rows, num_heads] int64 and
+ * log_probs [rows, num_heads] (per sub-head, not summed).
+ * num_heads <= MAPPO_MULTI_SAMPLE_MAX_HEADS, every head_sizes[k] >= 1, sum of head_sizes <= 64. */
+int mappo_multi_categorical_mode(const float* logits, const int* head_sizes, int num_heads, int64_t* actions,
+                                 float* log_probs, int64_t rows, mappo_stream_t stream);
+
 /* --------------------------------------------------------------- K8: GRU cell gates ----
  * Everything of one GRU step that is not a GEMM (reference onpolicy/algorithms/utils/rnn.py:7-80 runs
  * nn.GRU; PyTorch cell, gates stacked r|z|n), reading / writing the per-sequence buffers in place:

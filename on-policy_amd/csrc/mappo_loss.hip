@@ -441,25 +441,30 @@ extern "C" int mappo_ppo_loss_multi_f32(const mappo_ppo_loss_multi_t* args, mapp
 // drawn by the caller from torch's generator (graph-safe philox), so the distribution is exactly the framework's.
 // One thread per row; n_actions <= 64.
 
+// Logit i of a head as the distribution sees it: -1e10 where the action is unavailable (distributions.py:64-67).
+__device__ __forceinline__ float masked_logit(const float* lg, const float* av, int i) {
+    return (av && av[i] == 0.f) ? -1e10f : lg[i];
+}
+
 // One head of one row: the normalised logits of `lg[0..na)` (entries whose availability is 0 count as -1e10), the sampled
 // action argmax_i p_i / q_i and its log-probability.
 __device__ __forceinline__ void sample_head(const float* lg, const float* av, const float* q, int na, long long* action,
                                             float* logp) {
     float mx = -INFINITY;
     for (int i = 0; i < na; ++i) {
-        const float x = (av && av[i] == 0.f) ? -1e10f : lg[i];
+        const float x = masked_logit(lg, av, i);
         mx = fmaxf(mx, x);
     }
     float se = 0.f;
     for (int i = 0; i < na; ++i) {
-        const float x = (av && av[i] == 0.f) ? -1e10f : lg[i];
+        const float x = masked_logit(lg, av, i);
         se += expf(x - mx);
     }
     const float lse = mx + logf(se);
     int best = 0;
     float best_v = -1.f, best_l = 0.f;
     for (int i = 0; i < na; ++i) {
-        const float x = (av && av[i] == 0.f) ? -1e10f : lg[i];
+        const float x = masked_logit(lg, av, i);
         const float l = x - lse;                // normalised logit = log p_i
         const float v = expf(l) / q[i];         // p_i / q_i (first maximum wins, like argmax)
         if (v > best_v) {
@@ -529,6 +534,85 @@ extern "C" int mappo_multi_categorical_sample(const float* logits, const float* 
     }
     if (m.width > 64) return MAPPO_E_SHAPE;
     hipLaunchKernelGGL(multi_categorical_sample_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), logits, m, reinterpret_cast<long long*>(actions), log_probs,
+                       (long long)rows);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// K14 mode: the deterministic action of the Categorical head as one launch -- availability masking, the most probable
+// action and its log-probability (reference distributions.py:14-28 FixedCategorical.mode / log_probs behind
+// ACTLayer.forward's deterministic branches, act.py:44-60).  As framework ops that is where / logsumexp / softmax / argmax /
+// gather per head, plus a cat for MultiDiscrete.  softmax is monotone, so the mode is the first maximum of the masked
+// logits themselves: compared as float32, no tolerance.  One thread per row; the limits of K14.
+
+// One head of one row in two passes: maximum and its lowest index together, then the sum of exponentials.  The
+// log-probability is sample_head's l = x - lse at x = mx, where lse = mx + log(se): that is -log(se), and it is formed
+// so -- the float32 sum mx + log(se) rounds at the size of mx (3.8e-6 at |mx| ~ 100) before mx goes away again.
+__device__ __forceinline__ void mode_head(const float* lg, const float* av, int na, long long* action, float* logp) {
+    float mx = -INFINITY;
+    int best = 0;
+    for (int i = 0; i < na; ++i) {
+        const float x = masked_logit(lg, av, i);
+        if (x > mx) {                           // strict: the first maximum wins
+            mx = x;
+            best = i;
+        }
+    }
+    float se = 0.f;
+    for (int i = 0; i < na; ++i) se += expf(masked_logit(lg, av, i) - mx);
+    *action = best;
+    *logp = 0.f - logf(se);                     // (+0 where one action holds all the mass)
+}
+
+__global__ void __launch_bounds__(256) categorical_mode_kernel(const float* logits, const float* avail, long long* actions,
+                                                               float* logp, long long rows, int na) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    mode_head(logits + r * na, avail ? avail + r * na : nullptr, na, actions + r, logp + r);
+}
+
+extern "C" int mappo_categorical_mode(const float* logits, const float* available, int64_t* actions, float* log_probs,
+                                      int64_t rows, int n_actions, mappo_stream_t stream_) {
+    if (!logits || !actions || !log_probs) return MAPPO_E_NULL;
+    if (rows <= 0 || n_actions <= 0 || n_actions > 64) return MAPPO_E_SHAPE;
+    hipLaunchKernelGGL(categorical_mode_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream_), logits, available, reinterpret_cast<long long*>(actions),
+                       log_probs, (long long)rows, n_actions);
+    return (int)hipGetLastError();
+}
+
+// K14 mode for a MultiDiscrete head: every sub-head's mode and log-probability (no availability mask) in one launch, laid
+// out like the sampler's outputs.
+struct MultiModeArgs {
+    int size[MAPPO_MULTI_SAMPLE_MAX_HEADS];
+    int heads, width;
+};
+
+__global__ void __launch_bounds__(256) multi_categorical_mode_kernel(const float* logits, MultiModeArgs m,
+                                                                     long long* actions, float* logp, long long rows) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const float* lg = logits + r * m.width;
+    for (int h = 0; h < m.heads; ++h) {
+        mode_head(lg, nullptr, m.size[h], actions + r * m.heads + h, logp + r * m.heads + h);
+        lg += m.size[h];
+    }
+}
+
+extern "C" int mappo_multi_categorical_mode(const float* logits, const int* head_sizes, int num_heads, int64_t* actions,
+                                            float* log_probs, int64_t rows, mappo_stream_t stream_) {
+    if (!logits || !head_sizes || !actions || !log_probs) return MAPPO_E_NULL;
+    if (rows <= 0 || num_heads <= 0 || num_heads > MAPPO_MULTI_SAMPLE_MAX_HEADS) return MAPPO_E_SHAPE;
+    MultiModeArgs m = {};
+    m.heads = num_heads;
+    for (int h = 0; h < num_heads; ++h) {
+        if (head_sizes[h] <= 0) return MAPPO_E_SHAPE;
+        m.size[h] = head_sizes[h];
+        m.width += head_sizes[h];
+    }
+    if (m.width > 64) return MAPPO_E_SHAPE;
+    hipLaunchKernelGGL(multi_categorical_mode_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream_), logits, m, reinterpret_cast<long long*>(actions), log_probs,
                        (long long)rows);
     return (int)hipGetLastError();

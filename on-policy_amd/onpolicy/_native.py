@@ -173,6 +173,8 @@ SIGNATURES = {
     "mappo_ppo_loss_multi_f32": (_int, [ctypes.POINTER(PPOLossMulti), _vp]),
     "mappo_categorical_sample": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
     "mappo_multi_categorical_sample": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _i64, _vp]),
+    "mappo_categorical_mode": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _vp]),
+    "mappo_multi_categorical_mode": (_int, [_vp, _vp, _int, _vp, _vp, _i64, _vp]),
     "mappo_minibatch_workspace_ints": (_i64, [_i64, _int]),
     "mappo_minibatch_indices": (_int, [_i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "mappo_mlp_forward": (_int, [ctypes.POINTER(MLP), _vp]),

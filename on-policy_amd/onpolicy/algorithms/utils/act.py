@@ -23,6 +23,8 @@ class ACTLayer(nn.Module):
         self.multi_discrete = False
         self.mujoco_box = False
         self.action_type = kind = action_space.__class__.__name__
+        # opt-in (train_mpe.py's --use_device_eval): the deterministic action of Categorical heads from the mode form of K14
+        self.fused_mode = bool(getattr(args, "use_device_eval", False))
         if kind == "Discrete":
             self.action_out = Categorical(inputs_dim, action_space.n, use_orthogonal, gain)
         elif kind == "Box":
@@ -53,6 +55,13 @@ class ACTLayer(nn.Module):
             if fused_loss.multi_sample_supported(x, self.head_sizes):
                 # K14 for all sub-heads in one launch
                 return fused_loss.sample_multi_categorical(self.multi_logits(x), self.head_sizes)
+        if deterministic and self.fused_mode:
+            from . import fused_loss
+            if self.multi_discrete and fused_loss.mode_supported(x, self.head_sizes):
+                return fused_loss.mode_multi_categorical(self.multi_logits(x), self.head_sizes)     # K14 mode, all sub-heads
+            if self.action_type == "Discrete" and not torch.is_grad_enabled() and x.is_cuda:
+                # (from_logits asks mode_supported about the logits and keeps the framework's ops for what it refuses)
+                return self.from_logits(self.action_out.linear(x), available_actions, deterministic)
         if self.mixed_action or self.multi_discrete:
             actions, log_probs = [], []
             for head in self.action_outs:
@@ -84,6 +93,8 @@ class ACTLayer(nn.Module):
         from . import fused_loss
         if not deterministic and fused_loss.sample_supported(logits):
             return fused_loss.sample_categorical(logits, available_actions)      # K14: masking + sample + log-prob
+        if deterministic and self.fused_mode and fused_loss.mode_supported(logits):
+            return fused_loss.mode_categorical(logits, available_actions)        # K14 mode: masking + argmax + log-prob
         if available_actions is not None:
             logits = torch.where(available_actions == 0, torch.full_like(logits, -1e10), logits)
         dist = FixedCategorical(logits=logits)

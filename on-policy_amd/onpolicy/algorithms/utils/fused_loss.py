@@ -151,3 +151,50 @@ def sample_multi_categorical(logits, head_sizes):
                                                                _native.stream_of(lg.device)),
                   "mappo_multi_categorical_sample")
     return actions, logp
+
+
+def mode_supported(logits_or_x, head_sizes=None):
+    """The mode form of K14 takes this head's deterministic action: the conditions of ``sample_supported`` (a Discrete
+    head's logits) or, with ``head_sizes``, of ``multi_sample_supported`` (a MultiDiscrete head's features), without the
+    sampling-generator one -- the mode draws nothing.  ``MAPPO_FUSED_SAMPLE=0`` disables it with the samplers."""
+    x = logits_or_x
+    if not (os.environ.get("MAPPO_FUSED_SAMPLE", "1") != "0" and torch.is_tensor(x) and x.is_cuda
+            and x.dtype == torch.float32 and x.dim() == 2 and not torch.is_grad_enabled()):
+        return False
+    if head_sizes is None:
+        return 0 < x.shape[1] <= 64
+    return 0 < len(head_sizes) <= MULTI_SAMPLE_MAX_HEADS and sum(head_sizes) <= 64
+
+
+def mode_categorical(logits, available_actions=None):
+    """(actions [rows, 1] int64, log-probs [rows, 1]) of the most probable action per row of softmax(masked logits)
+    (``mappo_categorical_mode``, K14 mode): what ``Categorical.forward`` -> ``FixedCategorical.mode`` / ``log_probs``
+    give (reference distributions.py:14-28, :55-68) as one launch; of equal maxima the lowest index."""
+    rows, na = logits.shape
+    lg = logits.detach().contiguous()
+    avail = None if available_actions is None else available_actions.detach().to(torch.float32).contiguous()
+    assert avail is None or (avail.shape == lg.shape and avail.device == lg.device)
+    actions = torch.empty((rows, 1), dtype=torch.int64, device=lg.device)
+    logp = torch.empty((rows, 1), dtype=torch.float32, device=lg.device)
+    p = _native.ptr
+    _native.check(_native.lib().mappo_categorical_mode(p(lg), p(avail), p(actions), p(logp), rows, na,
+                                                       _native.stream_of(lg.device)), "mappo_categorical_mode")
+    return actions, logp
+
+
+def mode_multi_categorical(logits, head_sizes):
+    """(actions [rows, k] int64, log-probs [rows, k]) of every sub-head's most probable action from the sub-heads' logits
+    laid side by side in ``logits`` [rows, sum head_sizes] (``mappo_multi_categorical_mode``): what ACTLayer.forward's
+    multi-discrete branch gives with ``deterministic=True`` (reference act.py:44-60), as one launch."""
+    rows = logits.shape[0]
+    k = len(head_sizes)
+    assert logits.shape[1] == sum(head_sizes)
+    lg = logits.detach().contiguous()
+    actions = torch.empty((rows, k), dtype=torch.int64, device=lg.device)
+    logp = torch.empty((rows, k), dtype=torch.float32, device=lg.device)
+    p = _native.ptr
+    sizes = (ctypes.c_int * k)(*[int(n) for n in head_sizes])
+    _native.check(_native.lib().mappo_multi_categorical_mode(p(lg), sizes, k, p(actions), p(logp), rows,
+                                                             _native.stream_of(lg.device)),
+                  "mappo_multi_categorical_mode")
+    return actions, logp

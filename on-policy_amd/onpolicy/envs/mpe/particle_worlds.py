@@ -109,6 +109,17 @@ class TorchParticleWorlds(object):
         self._restart(self._torch.ones(self.n, dtype=self._torch.bool, device=self.device), self._fresh())
         return self._obs()
 
+    def reset_in_place(self):
+        """``reset()`` -- the same generator draws in the same order, the same state and observations bit for bit -- with
+        every tensor named by ``state_names`` kept at its address (``reset`` rebinds them): what a captured graph that
+        holds those addresses needs of a reset between its replays (runner/shared/eval_graph.py)."""
+        kept = {name: getattr(self, name) for name in self.state_names}
+        self._restart(self._torch.ones(self.n, dtype=self._torch.bool, device=self.device), self._fresh())
+        for name, tensor in kept.items():
+            tensor.copy_(getattr(self, name))
+            setattr(self, name, tensor)
+        return self._obs()
+
     @property
     def graph_safe(self):
         """True when ``step`` advances the state tensors IN PLACE (the kernel path): a captured rollout graph

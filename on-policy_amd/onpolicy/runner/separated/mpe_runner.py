@@ -182,7 +182,48 @@ class MPERunner(Runner):
         return [[one_hot[a][i] for a in range(self.num_agents)] for i in range(rnn_states.shape[0])]
 
     @torch.no_grad()
+    def _device_eval_step(self, obs, rnn_states, masks):
+        """One evaluation step on per-agent lists of tensors (eval worlds on the device): every agent's deterministic
+        actor on its own observation, the agents' integer actions side by side into the env step as ``collect`` does it,
+        masks and RNN states as ``eval`` keeps them (reference mpe_runner.py:188-222) -> (obs, rnn_states, masks: lists
+        per agent; rewards [N, A, 1]).  What the eager device loop runs and runner/separated/eval_graph.py captures."""
+        actions, states = [], []
+        for agent_id, tr in enumerate(self.trainer):
+            action, rnn_state = tr.policy.act(obs[agent_id], rnn_states[agent_id], masks[agent_id], deterministic=True)
+            actions.append(action)
+            states.append(rnn_state)
+        rows, rewards, dones, _ = self.eval_envs.step(torch.cat(actions, -1))
+        alive = torch.where(dones, 0.0, 1.0)                                                          # [N, A]
+        obs = [self.eval_envs.agent_obs(rows, agent_id).contiguous() for agent_id in range(self.num_agents)]
+        masks = [alive[:, agent_id:agent_id + 1].contiguous() for agent_id in range(self.num_agents)]
+        for agent_id, tr in enumerate(self.trainer):
+            if tr.policy.actor._recurrent:          # finished agents restart from a zero RNN state
+                states[agent_id] = states[agent_id] * masks[agent_id].view(-1, 1, 1)
+        return obs, states, masks, rewards
+
+    def _device_eval_begin(self, obs):
+        """-> (obs, rnn_states, masks), per agent, an evaluation starts from, given the rows of the worlds' reset."""
+        n, f32 = self.n_eval_rollout_threads, dict(dtype=torch.float32, device=obs.device)
+        agents = range(self.num_agents)
+        return ([self.eval_envs.agent_obs(obs, agent_id).contiguous() for agent_id in agents],
+                [torch.zeros(n, self.recurrent_N, self.hidden_size, **f32) for _ in agents],
+                [torch.ones(n, 1, **f32) for _ in agents])
+
+    @torch.no_grad()
     def eval(self, total_num_steps):
+        if getattr(self.eval_envs, "device_resident", False):
+            # eval worlds on the device (--use_device_eval): nothing crosses to the host but the totals, once
+            from onpolicy.runner.shared.eval_graph import totals
+            from onpolicy.runner.separated import eval_graph
+            for tr in self.trainer:
+                tr.prep_rollout()
+            sums = _t2n(totals(self, eval_graph.build))                                               # [N, A, 1]
+            eval_train_infos = []
+            for agent_id in range(self.num_agents):
+                mean = float(np.mean(sums[:, agent_id]))
+                eval_train_infos.append({'eval_average_episode_rewards': mean})
+                print("eval average episode rewards of agent%i: " % agent_id + str(mean))
+            return self.log_train(eval_train_infos, total_num_steps)
         n = self.n_eval_rollout_threads
         eval_episode_rewards = []
         eval_obs = self.eval_envs.reset()

@@ -48,14 +48,14 @@ class SeparatedRolloutGraph(shared.RolloutGraph):
             v, a, lp, ha, hc = tr.policy.get_actions(share, self.cur_obs[i], self.cur_rnn_a[i], self.cur_rnn_c[i],
                                                      self.cur_masks[i])
             values.append(v), actions.append(a), logp.append(lp), rnn_a.append(ha), rnn_c.append(hc)
-        obs, rewards, dones, infos = r.envs.step(torch.cat(actions, -1))
+        obs, rewards, dones, infos = self.envs.step(torch.cat(actions, -1))
         masks = torch.where(dones, 0.0, 1.0)                        # [N, A]: 0 where the episode ended (one launch)
         # the carried state of the next step; the slab writes take the static tensors as they are
         if r.use_centralized_V:
             self.cur_joint.copy_(obs)
         out = []
         for i in agents:
-            self.cur_obs[i].copy_(r.envs.agent_obs(obs, i))
+            self.cur_obs[i].copy_(self.envs.agent_obs(obs, i))
             self.cur_masks[i].copy_(masks[:, i:i + 1])
             if self.recurrent:
                 # finished agents restart from a zero RNN state (reference mpe_runner.py:151-154)

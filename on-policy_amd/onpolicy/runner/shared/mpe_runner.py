@@ -135,7 +135,35 @@ class MPERunner(Runner):
         return actions, rnn_states
 
     @torch.no_grad()
+    def _device_eval_step(self, obs, rnn_states, masks):
+        """One evaluation step on tensors [N, A, ...] (eval worlds on the device): the deterministic actor, the env step
+        on the integer actions as they are, masks and RNN states as ``eval`` keeps them (reference mpe_runner.py:151-180)
+        -> (obs, rnn_states, masks, rewards).  What the eager device loop runs and runner/shared/eval_graph.py captures."""
+        n = self.n_eval_rollout_threads
+        policy = self.trainer.policy
+        actions, rnn_states = policy.act(self._rows(obs), self._rows(rnn_states), self._rows(masks), deterministic=True)
+        obs, rewards, dones, _ = self.eval_envs.step(self._per_env(actions, n))
+        masks = torch.where(dones, 0.0, 1.0).unsqueeze(-1)          # 0 where the episode ended
+        rnn_states = self._per_env(rnn_states, n)
+        if policy.actor._recurrent:
+            rnn_states = rnn_states * masks.view(n, self.num_agents, 1, 1)      # finished agents restart from zero
+        return obs, rnn_states, masks, rewards
+
+    def _device_eval_begin(self, obs):
+        """-> (obs, rnn_states, masks) an evaluation starts from, given the observations of the worlds' reset."""
+        n, f32 = self.n_eval_rollout_threads, dict(dtype=torch.float32, device=obs.device)
+        return (obs, torch.zeros(n, self.num_agents, self.recurrent_N, self.hidden_size, **f32),
+                torch.ones(n, self.num_agents, 1, **f32))
+
+    @torch.no_grad()
     def eval(self, total_num_steps):
+        if getattr(self.eval_envs, "device_resident", False):
+            # eval worlds on the device (--use_device_eval): nothing crosses to the host but the totals, once
+            from onpolicy.runner.shared import eval_graph
+            self.trainer.prep_rollout()
+            totals = _t2n(eval_graph.totals(self))
+            print("eval average episode rewards of agent: " + str(np.mean(totals)))
+            return self.log_env({'eval_average_episode_rewards': totals}, total_num_steps)
         n = self.n_eval_rollout_threads
         eval_episode_rewards = []
         eval_obs = self.eval_envs.reset()

@@ -32,6 +32,7 @@ class RolloutGraph(object):
     def _init_common(self, runner, dev):
         """What ``capture`` / ``step`` read whatever the carried state looks like (the separated graph starts here too)."""
         self.r = runner
+        self.envs = runner.envs         # the worlds the step advances (the eval graph names the runner's eval worlds)
         self.N, self.A = runner.n_rollout_threads, runner.num_agents
         self.dev = dev
         self.popart = None
@@ -81,7 +82,7 @@ class RolloutGraph(object):
             values, rnn_c = r._per_env(values), r._per_env(rnn_c)
         actions, logp, rnn_a = policy.actor(r._rows(self.cur_obs), r._rows(self.cur_rnn_a), r._rows(self.cur_masks))
         actions, logp, rnn_a = r._per_env(actions), r._per_env(logp), r._per_env(rnn_a)
-        obs, rewards, dones, infos = r.envs.step(actions)
+        obs, rewards, dones, infos = self.envs.step(actions)
         masks = torch.where(dones, 0.0, 1.0).unsqueeze(-1)          # 0 where the episode ended (one launch)
         main.wait_stream(self.side)
         if self.recurrent:
@@ -100,10 +101,10 @@ class RolloutGraph(object):
 
     def _state_names(self):
         """The env's state tensors that a replay advances in place: what the env declares (``state_names``)."""
-        return tuple(self.r.envs.state_names)
+        return tuple(self.envs.state_names)
 
     def _env_state(self):
-        e = self.r.envs
+        e = self.envs
         return {k: getattr(e, k).clone() for k in self._state_names()}, e.rng.get_state(), \
             torch.cuda.get_rng_state(self.dev)
 
@@ -134,7 +135,7 @@ class RolloutGraph(object):
                 g.popart.weight.data, g.popart.bias.data = self.saved
 
     def _restore(self, snap):
-        e = self.r.envs
+        e = self.envs
         state, env_rng, dev_rng = snap
         for k, v in state.items():
             getattr(e, k).copy_(v)
@@ -150,7 +151,7 @@ class RolloutGraph(object):
         self.begin_episode()
         keep = [x.clone() for x in self._carried()]
         snap = self._env_state()
-        state_ptrs = {k: getattr(r.envs, k).data_ptr() for k in self._state_names()}
+        state_ptrs = {k: getattr(self.envs, k).data_ptr() for k in self._state_names()}
         torch.cuda.synchronize(dev)
         try:        # (warm-up included: whatever fails in here, worlds / generators / carried state go back where they were)
             with self._StaticHead(self):
@@ -162,12 +163,12 @@ class RolloutGraph(object):
                 torch.cuda.current_stream(dev).wait_stream(side)
                 torch.cuda.synchronize(dev)
                 graph = torch.cuda.CUDAGraph()
-                graph.register_generator_state(r.envs.rng)
+                graph.register_generator_state(self.envs.rng)
                 with capturing(graph):
                     self.out, self.infos = self._body()
                 torch.cuda.synchronize(dev)
             # the graph reads and advances the worlds IN PLACE: a step path that rebinds its state tensors cannot be replayed
-            moved = [k for k, p in state_ptrs.items() if getattr(r.envs, k).data_ptr() != p]
+            moved = [k for k, p in state_ptrs.items() if getattr(self.envs, k).data_ptr() != p]
             if moved:
                 raise RuntimeError("env.step rebinds its state tensors (%s): not capturable" % ", ".join(moved))
             self.graph = graph
@@ -210,13 +211,13 @@ def capturable(envs, device):
     return torch.device(device).type == "cuda" and distributions.SAMPLING_RNG == "device"
 
 
-def captured(make, device):
+def captured(make, device, what="rollout"):
     """``make().capture()``, or None where that fails: capture is an optimisation, anything it cannot take stays on the
     eager loop."""
     try:
         return make().capture()
     except Exception as exc:
-        print("rollout graph: capture failed (%s: %s); the rollout stays eager" % (type(exc).__name__, exc))
+        print("%s graph: capture failed (%s: %s); the %s stays eager" % (what, type(exc).__name__, exc, what))
         try:
             torch.cuda.synchronize(device)
         except Exception:

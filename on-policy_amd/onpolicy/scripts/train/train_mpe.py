@@ -9,7 +9,10 @@ simple_reference comes from the in-tree device implementation as well (envs/mpe/
 runner only), and so does simple_speaker_listener (envs/mpe/simple_speaker_listener.py: two agents with different
 spaces, so the separated runner only -- ``--share_policy`` -- with rmappo / mappo / ippo); every other case --
 simple_reference or simple_speaker_listener without the flag, any other scenario, and the eval envs of ``--use_eval``
-in every case -- is built per worker from an external env tree (MAPPO_ENVS_PATH); wandb / setproctitle are optional.
+in every case but one -- is built per worker from an external env tree (MAPPO_ENVS_PATH).  The exception:
+``--use_device_eval`` (with ``--use_eval --use_device_env``, rmappo / mappo / ippo) builds the eval worlds of the three
+device scenarios in-tree on the device too, and ``eval()`` then runs on tensors, its step as one captured graph launch
+(runner/shared/eval_graph.py).  wandb / setproctitle are optional.
 Example (BASELINE.json configs[0]):
     python -m onpolicy.scripts.train.train_mpe --env_name MPE --scenario_name simple_spread \\
         --num_agents 3 --num_landmarks 3 --n_rollout_threads 8 --episode_length 25 \\
@@ -79,6 +82,11 @@ def parse_args(args, parser):
                         help="rmappo / mappo / ippo with a MultiDiscrete action head (simple_reference) on a HIP device: "
                              "the PPO loss of all sub-heads as one kernel launch and the update as a captured graph "
                              "(MAPPO_FUSED_LOSS_MULTI=1 does the same)")
+    parser.add_argument('--use_device_eval', action='store_true', default=argparse.SUPPRESS,
+                        help="with --use_eval --use_device_env (rmappo / mappo / ippo): the eval worlds are held on the "
+                             "policy's device like the training worlds, eval() runs on tensors with the deterministic "
+                             "action from one kernel launch, and its step is replayed from a captured graph "
+                             "(MAPPO_EVAL_GRAPH=0: the eager tensor loop)")
     return parser.parse_known_args(args)[0]
 
 
@@ -91,6 +99,10 @@ def main(args):
     run_dir = _launch.new_run_dir(all_args, all_args.scenario_name)
     _launch.seed_everything(all_args)
     shared = all_args.share_policy and all_args.algorithm_name not in ("happo", "hatrpo")
+    device_eval = bool(getattr(all_args, "use_device_eval", False))
+    if device_eval and not (all_args.use_eval and all_args.use_device_env
+                            and all_args.algorithm_name in ("rmappo", "mappo", "ippo")):
+        raise NotImplementedError("--use_device_eval: with --use_eval and --use_device_env, rmappo / mappo / ippo only")
     if all_args.use_device_env:
         scenario = all_args.scenario_name
         separated = not shared and all_args.algorithm_name in ("rmappo", "mappo", "ippo")
@@ -100,7 +112,8 @@ def main(args):
                 "only" % (" / ".join(k for k in DEVICE_ENVS if k not in SEPARATED_DEVICE_ENVS),
                           " / ".join(SEPARATED_DEVICE_ENVS)))
     envs = make_train_env(all_args, device=device if all_args.use_device_env else None)
-    eval_envs = make_train_env(all_args, all_args.n_eval_rollout_threads, 50000) if all_args.use_eval else None
+    eval_envs = make_train_env(all_args, all_args.n_eval_rollout_threads, 50000,
+                               device=device if device_eval else None) if all_args.use_eval else None
     if shared:
         from onpolicy.runner.shared.mpe_runner import MPERunner as Runner
     else:
