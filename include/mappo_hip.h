@@ -321,6 +321,12 @@ int mappo_slab_copy_std(const mappo_slab_t* slabs, int n_slabs, const mappo_std_
  * `partials` is 3 * mappo_layernorm_max_blocks() * D floats when dpre_bias is requested (D <= 1024,
  * dx required), 2 * ... otherwise. */
 int mappo_layernorm_max_blocks(void);
+/* Which kernel shape the LayerNorm launchers and the standardising gather (mappo_field.standardize) take for rows of D
+ * floats: vec | lpr << 8 | epl << 16 (vec floats per access, lpr lanes per row, epl accesses per lane; a workgroup
+ * covers 256 / lpr rows per trip of its row loop), or 0 for a width they refuse with MAPPO_E_SHAPE.  aligned16 != 0:
+ * every operand starts on a 16-byte boundary; 0: some operand does not (float accesses, D <= 1536).  A host query:
+ * takes no pointers, launches nothing. */
+int mappo_layernorm_shape(int D, int aligned16);
 int mappo_bias_act_layernorm_fwd(const float* x, const float* pre_bias, const float* weight, const float* bias,
                                  float* y, float* mean, float* rstd, int64_t M, int D, float eps, int act,
                                  mappo_stream_t stream);

@@ -423,6 +423,20 @@ int mappo::gather_standardize(const float* src, float* dst, int width, long long
 
 extern "C" int mappo_layernorm_max_blocks(void) { return mappo::kCUs * 8; }
 
+// Which (VEC, LPR, EPL) the launchers take for rows of D floats: pick_shape on the stand-ins the launchers
+// themselves use -- the null pointer for operands on 16-byte boundaries, (void*)1 for the demotion.
+extern "C" int mappo_layernorm_shape(int D, int aligned16) {
+    if (D <= 0) return 0;
+    const void* p = aligned16 ? nullptr : (const void*)1;
+    Shape s = pick_shape(p, p, D);
+    if (s.epl == 0) return 0;
+    bool built = false;
+#define LN_SHAPE_BUILT(V, L, E) built = built || (s.vec == V && s.lpr == L && s.epl == E);
+    LN_FOR_SHAPES(LN_SHAPE_BUILT)
+#undef LN_SHAPE_BUILT
+    return built ? (s.vec | s.lpr << 8 | s.epl << 16) : 0;
+}
+
 extern "C" int mappo_bias_act_layernorm_fwd(const float* x, const float* pre_bias, const float* weight,
                                             const float* bias, float* y, float* mean, float* rstd, int64_t M,
                                             int D, float eps, int act, mappo_stream_t stream_) {

@@ -23,6 +23,15 @@ def supported(x, D):
     return (D % 4 == 0 and D <= 2048) or D <= 1536
 
 
+def _on_16_bytes(t, D):
+    """``t`` as the kernels can take it at width ``D``.  An operand off a 16-byte boundary (a contiguous view into a larger
+    buffer) makes the launchers read floats one by one, which they do for D <= 1536 only: wider rows are copied to
+    storage of their own (a fresh allocation starts on a boundary)."""
+    if t is None or D <= 1536 or t.data_ptr() % 16 == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 ACT_NONE, ACT_TANH, ACT_RELU = 0, 1, 2
 
 
@@ -38,14 +47,14 @@ class _LayerNormFn(torch.autograd.Function):
         from onpolicy import _native
         lib = _native.lib()
         D = x.shape[-1]
-        x2 = x.contiguous().view(-1, D)
+        x2 = _on_16_bytes(x.contiguous().view(-1, D), D)
         M = x2.shape[0]
         y = torch.empty_like(x2)
         mean = torch.empty(M, dtype=torch.float32, device=x.device)
         rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        w = weight.contiguous()
-        b = bias.contiguous()
-        pre = None if pre_bias is None else pre_bias.contiguous()
+        w = _on_16_bytes(weight.contiguous(), D)
+        b = _on_16_bytes(bias.contiguous(), D)
+        pre = None if pre_bias is None else _on_16_bytes(pre_bias.contiguous(), D)
         if M > 0:
             _native.check(lib.mappo_bias_act_layernorm_fwd(x2.data_ptr(), _native.ptr(pre), w.data_ptr(), b.data_ptr(),
                                                            y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), M, D,
@@ -62,7 +71,7 @@ class _LayerNormFn(torch.autograd.Function):
         lib = _native.lib()
         x2, w, mean, rstd, pre = ctx.saved_tensors
         M, D = x2.shape
-        dy2 = dy.contiguous().view(M, D)
+        dy2 = _on_16_bytes(dy.contiguous().view(M, D), D)
         want_pre = pre is not None and ctx.needs_input_grad[5]
         dx = torch.empty_like(x2) if (ctx.needs_input_grad[0] or want_pre) else None
         dw = torch.empty(D, dtype=torch.float32, device=x2.device)

@@ -230,11 +230,15 @@ class Judge(object):
         if os.path.exists(path):
             with open(path) as f:
                 doc = json.load(f)
-        doc["what"] = ("Small kernels (K7 loss, K13 clip + Adam) against float64 on the MI355X: per comparison the largest error of "
+        doc["what"] = ("Small kernels (K6 row normalisation, K7 loss, K13 clip + Adam) against float64 on the MI355X: per comparison the largest error of "
                        "the kernel and of the same float32 torch expression (overall and per case), each relative to the tensor's scale (sums: to sum "
                        "|per-row term|), the floor of the assert e_kernel <= 4 e_torch32 + floor (about 3 x the largest kernel "
                        "error; never above the 1e-5 it began at) and the worst e_kernel / bound.  Written by "
-                       "tests/test_gpu_fused_loss.py and tests/test_gpu_optim.py under MAPPO_MARGINS_JSON=<path>.")
+                       "tests/test_gpu_fused_loss.py, tests/test_gpu_optim.py and tests/test_gpu_row_norm.py under MAPPO_MARGINS_JSON=<path>.  "
+                       "k6.*: the LayerNorm kernels (y, mean, rstd, dx, dw, db, dpre), the standardising gather and the two standardisers of the "
+                       "resident copies (slab, rows_ld), per kernel shape v<VEC>.l<LPR>.e<EPL> or width; k6.narrow.*: rows of at most 16 floats, "
+                       "whose statistics are ill-conditioned in float32 whoever computes them; k6.*far.*: x = 100 + randn; k6.module: FusedLayerNorm "
+                       "on a contiguous view off a 16-byte boundary.")
         for name, rec in self.seen.items():
             old = doc.get(name)
             if old is not None and old.get("floor") == rec["floor"]:
