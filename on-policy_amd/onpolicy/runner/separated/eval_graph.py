@@ -39,8 +39,3 @@ class SeparatedEvalGraph(shared.EvalGraph):
     def _prep_rollout(self):
         for tr in self.r.trainer:
             tr.prep_rollout()
-
-
-def build(runner):
-    """-> a captured SeparatedEvalGraph for ``runner``, or None when the evaluation has to stay on the eager tensor loop."""
-    return shared.build(runner, SeparatedEvalGraph)

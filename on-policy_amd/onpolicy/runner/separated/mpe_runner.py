@@ -214,10 +214,10 @@ class MPERunner(Runner):
         if getattr(self.eval_envs, "device_resident", False):
             # eval worlds on the device (--use_device_eval): nothing crosses to the host but the totals, once
             from onpolicy.runner.shared.eval_graph import totals
-            from onpolicy.runner.separated import eval_graph
+            from onpolicy.runner.separated.eval_graph import SeparatedEvalGraph
             for tr in self.trainer:
                 tr.prep_rollout()
-            sums = _t2n(totals(self, eval_graph.build))                                               # [N, A, 1]
+            sums = _t2n(totals(self, SeparatedEvalGraph))                                             # [N, A, 1]
             eval_train_infos = []
             for agent_id in range(self.num_agents):
                 mean = float(np.mean(sums[:, agent_id]))

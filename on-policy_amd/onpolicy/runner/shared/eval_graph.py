@@ -101,13 +101,13 @@ def build(runner, make=EvalGraph):
 
 
 @torch.no_grad()
-def totals(runner, build=build):
+def totals(runner, make=EvalGraph):
     """The reward totals [N, A, 1] of one evaluation on ``runner``'s device-resident eval worlds, as a device tensor (kept
-    in ``runner.eval_totals``): ``episode_length`` replays of the captured step where ``build`` gives one -- asked once per
-    runner, on the first evaluation, and kept in ``runner.eval_graph`` -- and the eager tensor loop on
+    in ``runner.eval_totals``): ``episode_length`` replays of the captured step where ``make`` can be captured -- tried
+    once per runner, on the first evaluation, and kept in ``runner.eval_graph`` -- and the eager tensor loop on
     ``runner._device_eval_step`` otherwise.  The policies are in rollout mode already."""
     if not hasattr(runner, "eval_graph"):
-        runner.eval_graph = build(runner)
+        runner.eval_graph = build(runner, make)
     g = runner.eval_graph
     if g is not None:
         g.begin()

@@ -97,6 +97,35 @@ def test_graphed_rollout_equals_eager_rollout(tmp_path, monkeypatch, algo, extra
     np.testing.assert_allclose([[d["individual_reward"] for d in row] for row in g_infos], eager_infos, rtol=1e-6)
 
 
+def test_a_capture_that_fails_leaves_no_trace_in_the_eager_run(tmp_path, monkeypatch, capsys):
+    """A step that cannot be replayed (the worlds rebind a state tensor) ends ``capture`` through its own RuntimeError, after
+    warm-up and capture have advanced worlds, generators and carried state: all of it must be back where it was, so that the
+    run goes on eagerly exactly as a run that never tried (MAPPO_ROLLOUT_GRAPH=0): same buffers, same log, bit for bit."""
+    from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread
+    step = TorchSimpleSpread.step
+
+    def rebinding_step(self, actions):
+        out = step(self, actions)           # advances the worlds as before ...
+        self.pos = self.pos.clone()         # ... then moves one of the tensors named in ``state_names``
+        return out
+
+    monkeypatch.setattr(TorchSimpleSpread, "step", rebinding_step)
+    fields, logs = {}, {}
+    for mode in ("1", "0"):
+        runner = _runner(tmp_path / mode, monkeypatch, "mappo", N=8, T=4, episodes=2, graph=mode)
+        assert "pos" in runner.envs.state_names and runner.rollout_graph is None
+        # (the graphed run did try, and gave up for this reason; the other never tried)
+        said = "rollout graph: capture failed (RuntimeError: env.step rebinds its state tensors (pos)"
+        assert (said in capsys.readouterr().out) == (mode == "1")
+        torch.cuda.synchronize()
+        fields[mode] = {k: v.cpu().numpy() for k, v in _fields(runner).items()}
+        logs[mode] = open(os.path.join(runner.log_dir, "scalars.jsonl")).read()
+    assert fields["1"].keys() == fields["0"].keys() and {"obs", "actions", "rewards"} <= fields["1"].keys()
+    for name in fields["1"]:
+        np.testing.assert_array_equal(fields["1"][name], fields["0"][name], err_msg=name)
+    assert logs["1"] == logs["0"] and logs["1"].count("\n") > 2
+
+
 @pytest.mark.parametrize("extra", [(), POPART], ids=["valuenorm", "popart"])
 def test_training_through_the_graph_logs_like_the_eager_run(tmp_path, monkeypatch, extra):
     """Whole runs (rollouts + updates) with and without the graph from the same seed: same logged rewards / losses."""
