@@ -838,6 +838,79 @@ int mappo_simple_speaker_listener_step(double* pos, double* vel, double* landmar
                                        float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
                                        int world_length, int auto_reset, mappo_stream_t stream);
 
+/* ------------------------------------------------------------------- K16: Hanabi tables on the device ----
+ * The batched Hanabi stepper of include/hanabi_batch.h (libhanabi_batch.so, host) with its tables in device memory: the
+ * same rules, deal and encoder source (csrc/hanabi_rules.h), so for equal seeds and moves every row, reward, status and
+ * score equals the host stepper's -- and through it the reference engine's -- bit for bit.  What it replaces in the
+ * reference (marlbenchmark/on-policy) is what include/hanabi_batch.h lists: hanabi_lib/hanabi_state.cc:84-96, :164-283,
+ * :327-339, :364-382; hanabi_game.cc:50, :108-114, :162-196; canonical_encoders.cc:64-115, :133-182, :204-230, :259-342,
+ * :377-433, :482-536, :575-594; the per-env glue onpolicy/envs/hanabi/Hanabi_Env.py:278-312 (reset), :451-500 (step).
+ *
+ * The rule set is passed BY VALUE as the eight int32 fields of hanabi_rules_t in its order (colors, ranks, players,
+ * hand_size, max_information_tokens, max_life_tokens, observation_type, random_start_player), with its limits (5 colours,
+ * 5 ranks, 5 players, 5 cards a hand; tokens <= 1024).  random_start_player != 0 is MAPPO_E_SHAPE: that draw is a
+ * std::uniform_int_distribution, whose algorithm differs between library versions.  A rule set whose row image
+ * (observation | centralised row | legal moves) exceeds 48 KiB is MAPPO_E_SHAPE too.  share_mode: enum hanabi_share_mode.
+ *
+ * State is caller-owned: n_tables * mappo_hanabi_state_bytes(rules) bytes, 4-byte aligned, laid out by the library as
+ * the generators' words [624][n_tables] uint32 (word k of table n at k * n_tables + n: the tables of a wave touch
+ * neighbouring words) followed by n_tables game records (~240 bytes each, array of structs).  The library allocates
+ * nothing.  Row arrays are [n_tables, width] float32, 16-byte aligned (else MAPPO_E_ALIGN):
+ *   obs        width obs_len + players                  observation | one-hot turn of the player to move
+ *   share_obs  width own_hand_len + obs_len + players   (HANABI_SHARE_OWN_HAND) or players * obs_len + players
+ *   available  width num_moves                          1 where the move uid is legal
+ * to_move [n] int32 (may be NULL): the player to move, -1 for zero rows.
+ * flags [n] int32, the one word per table a host needs to drive the turn-based runner:
+ *   bits 0-7 status (0 running, 1 finished, 2 idle, 255 refused), bit 8 "some move is legal", bits 16-31 the score.
+ * Argument errors (MAPPO_E_NULL / _SHAPE / _ALIGN) are returned before anything touches the device. */
+
+/* Bytes of table state per table (negative: MAPPO_E_SHAPE for a rule set outside the limits). */
+int64_t mappo_hanabi_state_bytes(int32_t colors, int32_t ranks, int32_t players, int32_t hand_size,
+                                 int32_t max_information_tokens, int32_t max_life_tokens, int32_t observation_type,
+                                 int32_t random_start_player);
+/* dims[5] (HOST pointer) = players, num_moves (HanabiGame::MaxMoves), obs_len, own_hand_len, hand_size in force. */
+int mappo_hanabi_dims(int32_t colors, int32_t ranks, int32_t players, int32_t hand_size, int32_t max_information_tokens,
+                      int32_t max_life_tokens, int32_t observation_type, int32_t random_start_player, int32_t* dims);
+
+/* One generator per table from seeds[n] (device, int32 taken modulo 2^32) exactly as std::mt19937::seed does
+ * (hanabi_game.cc:50): s[0] = seed, s[k] = 1812433253 (s[k-1] ^ s[k-1] >> 30) + k, next word 624; the table is marked
+ * as not started and its draw counter is zeroed.  The generator keeps running across the games of its table. */
+int mappo_hanabi_seed(void* state, const int32_t* seeds, int64_t n_tables, mappo_stream_t stream);
+
+/* hanabi_batch_reset(choose) + hanabi_batch_encode(choose) (Hanabi_Env.py:278-312): a new game on every table with
+ * choose[n] != 0 (device uint8), dealt until a player is to move (hanabi_state.cc:327-339: discrete distribution over the
+ * card types in stock, written out -- weights stock / total in card order, normalised, running sums with the last set to
+ * 1, p from two generator words (low first) as a double in [0, 1), the first running sum >= p; one type left: no word
+ * is drawn), then its rows.  Tables not chosen keep their game and get zero rows, to_move -1, status 2.  Two launches. */
+int mappo_hanabi_reset(void* state, const uint8_t* choose, float* obs, float* share_obs, float* available,
+                       int32_t* to_move, int32_t* flags, int64_t n_tables, int share_mode, int32_t colors,
+                       int32_t ranks, int32_t players, int32_t hand_size, int32_t max_information_tokens,
+                       int32_t max_life_tokens, int32_t observation_type, int32_t random_start_player,
+                       mappo_stream_t stream);
+
+/* hanabi_batch_step + hanabi_batch_encode(actions != -1) (Hanabi_Env.py:451-500) as two launches: one thread per table
+ * applies actions[n] (device int32: move uid, or -1 to sit the move out) and deals (at most players * hand_size cards)
+ * until a player is to move, writing rewards [n] float32 (score differential), status [n] uint8, scores [n] int32 and
+ * flags; then one workgroup per table encodes the rows of the player now to move (zero rows for idle and refused
+ * tables).  UNLIKE the host call, which validates all moves first and applies none if one is illegal, an illegal or
+ * out-of-range uid -- or a table that was never reset -- leaves THAT table untouched and reports status 255 in its
+ * flags / status while the other tables advance: the caller reads the flags back and raises. */
+int mappo_hanabi_step(void* state, const int32_t* actions, float* rewards, uint8_t* status, int32_t* scores, float* obs,
+                      float* share_obs, float* available, int32_t* to_move, int32_t* flags, int64_t n_tables,
+                      int share_mode, int32_t colors, int32_t ranks, int32_t players, int32_t hand_size,
+                      int32_t max_information_tokens, int32_t max_life_tokens, int32_t observation_type,
+                      int32_t random_start_player, mappo_stream_t stream);
+
+/* hanabi_batch_encode alone: the rows of every started table with active[n] != 0 (device uint8; NULL: all), zero rows
+ * for the others (canonical_encoders.cc, sections as listed above).  One launch. */
+int mappo_hanabi_encode(const void* state, const uint8_t* active, float* obs, float* share_obs, float* available,
+                        int32_t* to_move, int64_t n_tables, int share_mode, int32_t colors, int32_t ranks,
+                        int32_t players, int32_t hand_size, int32_t max_information_tokens, int32_t max_life_tokens,
+                        int32_t observation_type, int32_t random_start_player, mappo_stream_t stream);
+
+/* draws[n] int32 (device): 32-bit words each table's generator has produced since mappo_hanabi_seed (tests, tools). */
+int mappo_hanabi_draws(const void* state, int32_t* draws, int64_t n_tables, mappo_stream_t stream);
+
 /* --------------------------------------------------------------------- misc ---- */
 int         mappo_abi_version(void);
 const char* mappo_build_info(void);        /* "gfx950 ..." static string */

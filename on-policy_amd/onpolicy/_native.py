@@ -119,6 +119,8 @@ class Adam(ctypes.Structure):
 
 LOSS_HUBER, LOSS_CLIPPED_VALUE, LOSS_POLICY_ACTIVE_MASKS, LOSS_VALUE_ACTIVE_MASKS = 1, 2, 4, 8
 
+_RULES = [ctypes.c_int32] * 8
+
 # symbol -> (restype, argtypes); must list every function include/mappo_hip.h declares
 SIGNATURES = {
     "mappo_gae_f32": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _i64,
@@ -199,6 +201,14 @@ SIGNATURES = {
     "mappo_simple_spread_step": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_reference_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
     "mappo_simple_speaker_listener_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
+    # K16: the eight int32 fields of hanabi_rules_t travel by value (``_RULES``)
+    "mappo_hanabi_state_bytes": (_i64, _RULES),
+    "mappo_hanabi_dims": (_int, _RULES + [_vp]),
+    "mappo_hanabi_seed": (_int, [_vp, _vp, _i64, _vp]),
+    "mappo_hanabi_reset": (_int, [_vp] * 7 + [_i64, _int] + _RULES + [_vp]),
+    "mappo_hanabi_step": (_int, [_vp] * 10 + [_i64, _int] + _RULES + [_vp]),
+    "mappo_hanabi_encode": (_int, [_vp] * 6 + [_i64, _int] + _RULES + [_vp]),
+    "mappo_hanabi_draws": (_int, [_vp, _vp, _i64, _vp]),
     "mappo_abi_version": (_int, []),
     "mappo_build_info": (ctypes.c_char_p, []),
     "mappo_error_string": (ctypes.c_char_p, [_int]),

@@ -19,6 +19,14 @@ policy's device (``_TurnState``: one tensor per buffer field, [N, A, ...]):
 
 The host keeps what decides control flow: the legal-move table (who moves), the done flags (which
 games reset) and the scores.  Control flow and the order of the env calls are the reference's.
+
+With device-resident tables (``envs.device_resident``: ``HanabiDeviceVecEnv``, ``--use_device_env``) the env's rows
+are device tensors already: ``use_obs`` / ``use_share_obs`` / ``use_available_actions`` ARE the env's tensors (no
+``_HostStage`` upload), the actions reach the env as a device tensor (-1 everywhere, the policy's action where a
+player moves), restarted games' rows are merged in with ``torch.where``, and ``avail_host`` shrinks to the [N, 1]
+"can move" column.  One small device -> host copy per move remains -- one int32 flags word per table (status, can
+move, score): the host still decides who moves and which games restart, so control flow and the order of the env
+calls are unchanged.
 """
 import time
 
@@ -80,11 +88,17 @@ class HanabiRunner(Runner):
     def __init__(self, config):
         super(HanabiRunner, self).__init__(config)
         self.true_total_num_steps = 0
+        self._device_env = bool(getattr(self.envs, "device_resident", False))
 
-    def run(self):
+    def begin_rollout(self):
+        """Turn state, staging area and the first deal: what run() sets up before its first buffer step."""
         self.turn = _TurnState(self.n_rollout_threads, self.buffer, self.buffer.device)
         self._stage = _HostStage(self.buffer.device)
+        self.scores = []
         self.warmup()
+
+    def run(self):
+        self.begin_rollout()
         start = time.time()
         episodes = int(self.num_env_steps) // self.episode_length // self.n_rollout_threads_job
         T = self.episode_length
@@ -110,19 +124,7 @@ class HanabiRunner(Runner):
                     self.compute()
                     train_infos = self.train()
 
-                b.chooseinsert(turn.share_obs, turn.obs, turn.rnn_states, turn.rnn_states_critic, turn.actions,
-                               turn.action_log_probs, turn.values, turn.rewards, turn.masks, turn.bad_masks,
-                               turn.active_masks, turn.available_actions)
-                obs, share_obs, available_actions = self.envs.reset(self.reset_choose)
-                share_obs = share_obs if self.use_centralized_V else obs
-                rc = self.reset_choose
-                if rc.any():        # only the restarted games' rows cross to the device
-                    rows = torch.as_tensor(np.flatnonzero(rc), device=self.buffer.device)
-                    o_d, s_d, a_d = self._stage.upload([obs[rc], share_obs[rc], available_actions[rc]])
-                    self.use_obs[rows] = o_d
-                    self.use_share_obs[rows] = s_d
-                    self.use_available_actions[rows] = a_d
-                    self.avail_host[rc] = available_actions[rc]
+                self.insert_and_restart()
 
             total_num_steps = (episode + 1) * T * self.n_rollout_threads_job
             if episode % self.save_interval == 0 or episode == episodes - 1:
@@ -142,11 +144,46 @@ class HanabiRunner(Runner):
             if episode % self.eval_interval == 0 and self.use_eval:
                 self.eval(self.true_total_num_steps)
 
+    def insert_and_restart(self):
+        """The turn just played -> the buffer; then new games on the tables ``collect`` marked, their rows merged in."""
+        b, turn = self.buffer, self.turn
+        b.chooseinsert(turn.share_obs, turn.obs, turn.rnn_states, turn.rnn_states_critic, turn.actions,
+                       turn.action_log_probs, turn.values, turn.rewards, turn.masks, turn.bad_masks,
+                       turn.active_masks, turn.available_actions)
+        obs, share_obs, available_actions = self.envs.reset(self.reset_choose)
+        share_obs = share_obs if self.use_centralized_V else obs
+        rc = self.reset_choose
+        if rc.any() and self._device_env:       # restarted games' rows replace the old ones, on the device
+            restarted = torch.as_tensor(rc, device=self.buffer.device).view(-1, 1)
+            self.use_obs = torch.where(restarted, obs, self.use_obs)
+            self.use_share_obs = torch.where(restarted, share_obs, self.use_share_obs)
+            self.use_available_actions = torch.where(restarted, available_actions, self.use_available_actions)
+            self.avail_host[rc] = self.envs.can_move()[rc]
+        elif rc.any():      # only the restarted games' rows cross to the device
+            rows = torch.as_tensor(np.flatnonzero(rc), device=self.buffer.device)
+            o_d, s_d, a_d = self._stage.upload([obs[rc], share_obs[rc], available_actions[rc]])
+            self.use_obs[rows] = o_d
+            self.use_share_obs[rows] = s_d
+            self.use_available_actions[rows] = a_d
+            self.avail_host[rc] = available_actions[rc]
+
     def warmup(self):
         self.reset_choose = np.ones(self.n_rollout_threads, dtype=bool)
         obs, share_obs, available_actions = self.envs.reset(self.reset_choose)
         share_obs = share_obs if self.use_centralized_V else obs
-        self._take_env_rows(obs, share_obs, available_actions)
+        if self._device_env:
+            self._take_device_rows(obs, share_obs, available_actions)
+        else:
+            self._take_env_rows(obs, share_obs, available_actions)
+
+    def _take_device_rows(self, obs, share_obs, available_actions):
+        """Device-resident tables: the env's tensors are the current rows as they are (valid until its next step);
+        of the legal-move table the host keeps the "can move" column, read off the flags words.
+        -> (done, alive) of the call just made, on the device."""
+        self.use_obs, self.use_share_obs, self.use_available_actions = obs, share_obs, available_actions
+        self.avail_host = self.envs.can_move()
+        status = self.envs.flags_device & 0xff
+        return status == 1, status == 0
 
     def _take_env_rows(self, obs, share_obs, available_actions, extra=()):
         """The env's current rows -> device (``use_*``); the legal-move table also stays on the host, where it
@@ -162,7 +199,10 @@ class HanabiRunner(Runner):
         turn, n, A = self.turn, self.n_rollout_threads, self.num_agents
         dev = self.buffer.device
         for agent_id in range(A):
-            env_actions = -np.ones((n,) + tuple(self.buffer.actions.shape[3:]), dtype=np.float32)
+            if self._device_env:
+                env_actions = torch.full((n,) + tuple(self.buffer.actions.shape[3:]), -1, dtype=torch.int32, device=dev)
+            else:
+                env_actions = -np.ones((n,) + tuple(self.buffer.actions.shape[3:]), dtype=np.float32)
             choose = np.any(self.avail_host == 1, axis=1)    # envs whose player can move
             if not np.any(choose):
                 self.reset_choose = np.ones(n, dtype=bool)
@@ -177,14 +217,18 @@ class HanabiRunner(Runner):
             value, action, action_log_prob, rnn_state, rnn_state_critic = self.trainer.policy.get_actions(
                 share_c, obs_c, turn.rnn_states[sel, agent_id], turn.rnn_states_critic[sel, agent_id],
                 turn.masks[sel, agent_id], avail_c)
-            action_np = _t2n(action)             # the one device -> host transfer of a move: the env needs the actions
+            if not self._device_env:
+                action_np = _t2n(action)         # the one device -> host transfer of a move: the env needs the actions
             to = dict(device=dev, dtype=torch.float32)
             turn.obs[sel, agent_id] = obs_c
             turn.share_obs[sel, agent_id] = share_c
             turn.available_actions[sel, agent_id] = avail_c
             turn.values[sel, agent_id] = value.to(**to)
             turn.actions[sel, agent_id] = action.to(**to)
-            env_actions[sel_host] = action_np
+            if self._device_env:
+                env_actions[sel] = action.to(torch.int32).reshape((-1,) + tuple(env_actions.shape[1:]))
+            else:
+                env_actions[sel_host] = action_np
             turn.action_log_probs[sel, agent_id] = action_log_prob.to(**to)
             turn.rnn_states[sel, agent_id] = rnn_state.to(**to)
             turn.rnn_states_critic[sel, agent_id] = rnn_state_critic.to(**to)
@@ -194,10 +238,14 @@ class HanabiRunner(Runner):
             share_obs = share_obs if self.use_centralized_V else obs
             done = np.asarray(dones) == True   # noqa: E712  (dones may hold None for idle envs)
             alive = np.asarray(dones) == False  # noqa: E712
-            rewards_d, done_d, alive_d = self._take_env_rows(
-                obs, share_obs, available_actions,
-                extra=[np.asarray(rewards, dtype=np.float32).reshape(turn.rewards.shape), done, alive])
-            done_d, alive_d = done_d > 0, alive_d > 0
+            if self._device_env:
+                done_d, alive_d = self._take_device_rows(obs, share_obs, available_actions)
+                rewards_d = rewards.reshape(turn.rewards.shape)
+            else:
+                rewards_d, done_d, alive_d = self._take_env_rows(
+                    obs, share_obs, available_actions,
+                    extra=[np.asarray(rewards, dtype=np.float32).reshape(turn.rewards.shape), done, alive])
+                done_d, alive_d = done_d > 0, alive_d > 0
 
             # the acting player collects what accumulated since its previous move; everybody accrues
             # the new reward (the reward of buffer step 0 is discarded by the shift in run())

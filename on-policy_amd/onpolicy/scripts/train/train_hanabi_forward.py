@@ -4,9 +4,12 @@ onpolicy/scripts/train/train_hanabi_forward.py (parse_args :61-69, env factories
 The env is the in-tree batched stepper (``onpolicy.envs.hanabi``): all rollout threads advance in one native
 call (``HanabiBatchVecEnv``).  ``--use_subproc_envs`` builds the reference's layout instead -- one ``HanabiEnv``
 per thread behind ``ChooseSubprocVecEnv`` / ``ChooseDummyVecEnv``; both give identical games for the same seeds.
+``--use_device_env`` keeps the TRAINING tables in device memory instead (``HanabiDeviceVecEnv``: HIP stepper and encoder,
+same games again); evaluation stays on the host stepper.
 
     python -m onpolicy.scripts.train.train_hanabi_forward --env_name Hanabi --hanabi_name Hanabi-Full --num_agents 2 ...
 """
+import argparse
 import sys
 
 from onpolicy.config import get_config
@@ -14,10 +17,14 @@ from onpolicy.envs.env_wrappers import ChooseDummyVecEnv, ChooseSubprocVecEnv
 from onpolicy.scripts.train import _launch
 
 
-def make_env(all_args, n_threads, seed_of_rank):
+def make_env(all_args, n_threads, seed_of_rank, device=None):
+    """``device``: build the tables in that device's memory (the training envs under ``--use_device_env``)."""
     if all_args.env_name != "Hanabi":
         raise NotImplementedError("Can not support the " + all_args.env_name + " environment.")
     assert 1 < all_args.num_agents < 6, "num_agents can be only between 2-5."
+    if device is not None:
+        from onpolicy.envs.hanabi.device import HanabiDeviceVecEnv
+        return HanabiDeviceVecEnv(all_args, [seed_of_rank(rank) for rank in range(n_threads)], device)
     if not all_args.use_subproc_envs:
         from onpolicy.envs.hanabi.batch import HanabiBatchVecEnv
         # the runner copies every row it keeps, so the stepper's own arrays are handed out as they are
@@ -44,15 +51,26 @@ def parse_args(args, parser):
     parser.add_argument('--use_subproc_envs', action='store_true', default=False,
                         help="one HanabiEnv per rollout thread behind the Choose* VecEnv wrappers (reference layout) "
                              "instead of the batched stepper")
+    # opt-in and absent from the namespace unless given (main() reads it as False then): a run without it parses
+    # exactly as before
+    parser.add_argument('--use_device_env', action='store_true', default=argparse.SUPPRESS,
+                        help="keep the training tables on the GPU (HIP stepper and encoder); evaluation stays on the "
+                             "host stepper")
     return parser.parse_known_args(args)[0]
 
 
 def main(args):
     all_args = _launch.apply_algorithm_flags(parse_args(args, get_config()), ("rmappo", "mappo", "ippo"))
+    all_args.use_device_env = bool(getattr(all_args, "use_device_env", False))
     device = _launch.device_of(all_args)
+    if all_args.use_device_env and all_args.use_subproc_envs:
+        raise NotImplementedError("--use_device_env and --use_subproc_envs are two different env layouts: pick one")
+    if all_args.use_device_env and device.type != "cuda":
+        raise NotImplementedError("--use_device_env needs a GPU device (the tables live in its memory)")
     run_dir = _launch.new_run_dir(all_args, all_args.hanabi_name)
     _launch.seed_everything(all_args)
-    envs = make_env(all_args, all_args.n_rollout_threads, lambda rank: all_args.seed + (getattr(all_args, "rollout_thread_offset", 0) + rank) * 1000)
+    envs = make_env(all_args, all_args.n_rollout_threads, lambda rank: all_args.seed + (getattr(all_args, "rollout_thread_offset", 0) + rank) * 1000,
+                    device=device if all_args.use_device_env else None)
     eval_envs = make_env(all_args, all_args.n_eval_rollout_threads,
                          lambda rank: all_args.seed * 50000 + rank * 10000) if all_args.use_eval else None
     if not all_args.share_policy:
