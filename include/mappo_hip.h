@@ -911,6 +911,76 @@ int mappo_hanabi_encode(const void* state, const uint8_t* active, float* obs, fl
 /* draws[n] int32 (device): 32-bit words each table's generator has produced since mappo_hanabi_seed (tests, tools). */
 int mappo_hanabi_draws(const void* state, int32_t* draws, int64_t n_tables, mappo_stream_t stream);
 
+/* ------------------------------------------------- K17: the turn bookkeeping of a Hanabi move, from the flags words ----
+ * What HanabiRunner.collect does around the env step of one player's move (reference
+ * onpolicy/runner/shared/hanabi_runner_forward.py:138-220: the masked numpy assignments on the arrays shaped like a buffer
+ * row, the choose / reset_choose decisions, the score list, true_total_num_steps) as two launches that read "who moves"
+ * and "which games ended" off device memory -- bit 8 and the status byte of K16's flags words -- so that a move needs no
+ * device -> host copy.  All operands of one move travel in one descriptor:
+ *   turn tensors, contiguous [n_tables, players, W] float32 (W = obs_w / share_w / avail_w for the three row fields, 1 for
+ *     the others): obs, share_obs, available_actions, values, actions, action_log_probs, rewards,
+ *     rewards_since_last_action, masks, active_masks;
+ *   current rows [n_tables, W]: use_obs, use_share_obs (may alias use_obs), use_available_actions;
+ *   the policy's outputs [n_tables]: value, action (int64), logp;   the env's: flags (int32, K16), rewards_env;
+ *   the route's state [n_tables]: can_move (int32), reset_choose (uint8), env_actions (int32), and the per-table
+ *     accumulators moves (int64), games, score_sum (int32), refused (uint8) -- summed on the host, so nothing is atomic
+ *     and nothing depends on order.
+ * The six row arrays must be 16-byte aligned, moves and action 8-byte, everything else 4-byte (uint8 arrays: any).
+ *
+ * mappo_hanabi_turn_begin(agent), per table n with m = can_move[n] != 0:
+ *   env_actions[n] = m ? (int32) action[n] : -1;  if m: rows [n, agent] of obs / share_obs / available_actions = the
+ *   current rows of n, values[n, agent] = value[n], actions[n, agent] = (float) action[n],
+ *   action_log_probs[n, agent] = logp[n].  A table that sits out has nothing else written.
+ * mappo_hanabi_turn_end(agent), per table n with status = flags[n] & 0xff, m as turn_begin read it, in this order:
+ *   if m:            rewards[n, agent] = rsla[n, agent]; rsla[n, agent] = 0; rsla[n, a] += rewards_env[n] for every a;
+ *                    moves[n] += 1                                   (rsla = rewards_since_last_action)
+ *   if status == 0:  masks[n, agent] = active_masks[n, agent] = 1
+ *   if status == 1:  reset_choose[n] = 1; games[n] += 1; score_sum[n] += flags[n] >> 16; row n of use_available_actions
+ *                    = 0; masks[n, :] = 0; active_masks[n, agent] = 1; for every a > agent: active_masks[n, a] = 0,
+ *                    rewards[n, a] = rsla[n, a], rsla[n, a] = 0, values[n, a] = 0, rows [n, a] of obs and share_obs = 0
+ *   if status == 255: refused[n] = 1 (sticky)
+ *   can_move[n] = status == 1 ? 0 : (flags[n] >> 8) & 1
+ * One wave per table, at most MAPPO_TURN_MAX_BLOCKS workgroups of four waves striding over the tables; rows are moved
+ * 16 bytes per lane wherever source and destination share their offset from a 16-byte boundary (else 4-byte loads,
+ * 16-byte stores).  MAPPO_E_NULL (a pointer the call reads or writes; the other call's may be NULL), MAPPO_E_SHAPE (n_tables <= 0, players outside [1, 5], agent outside
+ * [0, players), a width <= 0) and MAPPO_E_ALIGN are returned before anything is enqueued. */
+#define MAPPO_TURN_MAX_BLOCKS 2048
+#define MAPPO_TURN_MAX_PLAYERS 5
+typedef struct mappo_hanabi_turn {
+    float* obs;
+    float* share_obs;
+    float* available_actions;
+    float* values;
+    float* actions;
+    float* action_log_probs;
+    float* rewards;
+    float* rewards_since_last_action;
+    float* masks;
+    float* active_masks;
+    float* use_obs;
+    float* use_share_obs;
+    float* use_available_actions;
+    const float* value;
+    const int64_t* action;
+    const float* logp;
+    const int32_t* flags;
+    const float* rewards_env;
+    int32_t* can_move;
+    uint8_t* reset_choose;
+    int32_t* env_actions;
+    int64_t* moves;
+    int32_t* games;
+    int32_t* score_sum;
+    uint8_t* refused;
+    int64_t n_tables;
+    int32_t players;
+    int32_t obs_w;
+    int32_t share_w;
+    int32_t avail_w;
+} mappo_hanabi_turn_t;
+int mappo_hanabi_turn_begin(const mappo_hanabi_turn_t* args, int agent, mappo_stream_t stream);
+int mappo_hanabi_turn_end(const mappo_hanabi_turn_t* args, int agent, mappo_stream_t stream);
+
 /* --------------------------------------------------------------------- misc ---- */
 int         mappo_abi_version(void);
 const char* mappo_build_info(void);        /* "gfx950 ..." static string */

@@ -117,6 +117,19 @@ class Adam(ctypes.Structure):
                [("grad_norm", _vp), ("workspace", _vp), ("lr_device", _vp)]
 
 
+TURN_MAX_BLOCKS, TURN_MAX_PLAYERS = 2048, 5       # MAPPO_TURN_MAX_BLOCKS (of four waves, one wave per table), _MAX_PLAYERS
+
+
+class HanabiTurn(ctypes.Structure):
+    """struct mappo_hanabi_turn (include/mappo_hip.h): every operand of K17's two launches."""
+    _fields_ = [(n, _vp) for n in ("obs", "share_obs", "available_actions", "values", "actions", "action_log_probs",
+                                   "rewards", "rewards_since_last_action", "masks", "active_masks", "use_obs",
+                                   "use_share_obs", "use_available_actions", "value", "action", "logp", "flags",
+                                   "rewards_env", "can_move", "reset_choose", "env_actions", "moves", "games",
+                                   "score_sum", "refused")] + \
+               [("n_tables", _i64)] + [(n, ctypes.c_int32) for n in ("players", "obs_w", "share_w", "avail_w")]
+
+
 LOSS_HUBER, LOSS_CLIPPED_VALUE, LOSS_POLICY_ACTIVE_MASKS, LOSS_VALUE_ACTIVE_MASKS = 1, 2, 4, 8
 
 _RULES = [ctypes.c_int32] * 8
@@ -209,6 +222,9 @@ SIGNATURES = {
     "mappo_hanabi_step": (_int, [_vp] * 10 + [_i64, _int] + _RULES + [_vp]),
     "mappo_hanabi_encode": (_int, [_vp] * 6 + [_i64, _int] + _RULES + [_vp]),
     "mappo_hanabi_draws": (_int, [_vp, _vp, _i64, _vp]),
+    # K17
+    "mappo_hanabi_turn_begin": (_int, [ctypes.POINTER(HanabiTurn), _int, _vp]),
+    "mappo_hanabi_turn_end": (_int, [ctypes.POINTER(HanabiTurn), _int, _vp]),
     "mappo_abi_version": (_int, []),
     "mappo_build_info": (ctypes.c_char_p, []),
     "mappo_error_string": (ctypes.c_char_p, [_int]),

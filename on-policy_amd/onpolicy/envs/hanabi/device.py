@@ -6,7 +6,9 @@ launches (apply + deal by one thread per table, encode by one workgroup per tabl
 ``HanabiDeviceVecEnv`` gives them the ``reset(reset_choose)`` / ``step(actions)`` contract of ``HanabiBatchVecEnv``.
 
 What still crosses to the host is one int32 *flags word* per table and move (status | can-move << 8 | score << 16,
-``FLAG_*`` below): the turn-based runner decides on the host who moves and which games restart.
+``FLAG_*`` below): the turn-based runner decides on the host who moves and which games restart.  The runner's opt-in
+"device turns" route reads those words on the device instead (K17, runner/shared/hanabi_turns.py) and drives the tables
+through ``HanabiDeviceVecEnv.step_device`` / ``reset_device``, which launch and read nothing back.
 
 One difference to the host stepper: ``hanabi_batch_step`` validates every move before it applies any, so an illegal move
 leaves ALL tables untouched.  The device step leaves only the offending table untouched (status 255); by the time the
@@ -214,6 +216,44 @@ class HanabiDeviceVecEnv(object):
         dones = _DONE_OF_STATUS[flag_status(self.flags)]
         infos = _ScoreInfos(flag_score(self.flags))
         return b.obs, b.share_obs, rewards, dones, infos, b.available_actions
+
+    # ---- the host-free contract of the "device turns" route (runner/shared/hanabi_turns.py): launches only, no readback.
+    # ``self.flags`` / ``flags_device`` / ``can_move()`` belong to the calls above and are NOT kept current by these.
+    graph_safe = True       # step_device advances the tensors ``state_names`` lists in place: a capture can replay it
+    state_names = ("table_state", "step_obs", "step_share_obs", "step_available_actions", "step_to_move", "step_flags",
+                   "step_rewards", "step_status", "step_scores")
+    table_state = property(lambda self: self.batch._state)      # the tables and their generators
+    step_obs = property(lambda self: self.batch.rows.obs)
+    step_share_obs = property(lambda self: self.batch.rows.share_obs)
+    step_available_actions = property(lambda self: self.batch.rows.available_actions)
+    step_to_move = property(lambda self: self.batch.rows.to_move)
+    step_flags = property(lambda self: self.batch.rows.flags)
+    step_rewards = property(lambda self: self.batch.rewards)      # [n]: every player of a table gets the same reward
+    step_status = property(lambda self: self.batch.status)
+    step_scores = property(lambda self: self.batch.scores)
+
+    def step_device(self, env_actions):
+        """``env_actions`` [n] int32 on the device, taken as it is (-1: the table sits out) -> the two launches of a move.
+        Results: ``step_obs`` / ``step_share_obs`` / ``step_available_actions`` / ``step_flags`` / ``step_rewards`` -- the same
+        tensors every call.  A refused move shows as status 255 in ``step_flags``; nothing is read back, nothing raised."""
+        b, rows = self.batch, self.batch.rows
+        assert env_actions.dtype == torch.int32 and env_actions.shape == (b.n,) and env_actions.is_contiguous() \
+            and env_actions.device == b.device
+        with torch.cuda.device(b.device):
+            _native.check(b._lib.mappo_hanabi_step(
+                b._state.data_ptr(), env_actions.data_ptr(), b.rewards.data_ptr(), b.status.data_ptr(),
+                b.scores.data_ptr(), rows.obs.data_ptr(), rows.share_obs.data_ptr(), rows.available_actions.data_ptr(),
+                rows.to_move.data_ptr(), rows.flags.data_ptr(), b.n, b.share_mode, *(b._rules + (b._stream(),))),
+                "mappo_hanabi_step")
+
+    def reset_device(self, mask):
+        """``mask`` [n] uint8 on the device: new games where it is set -- none where it is all zero; the two launches run
+        either way.  -> (obs, share_obs, available_actions, flags) of the reset: the same tensors every call, zero rows
+        and status idle for the tables it left alone.  Nothing is read back."""
+        b, rows = self.batch, self._reset_rows
+        assert mask.dtype == torch.uint8 and mask.shape == (b.n,) and mask.is_contiguous() and mask.device == b.device
+        b.reset(mask, into=rows, readback=False)
+        return rows.obs, rows.share_obs, rows.available_actions, rows.flags
 
     def close(self):
         self.batch.close()

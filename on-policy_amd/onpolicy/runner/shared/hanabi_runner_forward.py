@@ -27,7 +27,21 @@ player moves), restarted games' rows are merged in with ``torch.where``, and ``a
 "can move" column.  One small device -> host copy per move remains -- one int32 flags word per table (status, can
 move, score): the host still decides who moves and which games restart, so control flow and the order of the env
 calls are unchanged.
+
+"Device turns" (``train_hanabi_forward.py --use_device_env --use_device_turns``, opt-in) removes that copy as well: who moves
+and which games restart are read off the flags words ON the device (runner/shared/hanabi_turns.py: K17's two launches
+around the env step), the policy runs on ALL N rows of static current-row tensors (a table that sits out has an all-zero
+legal-move row; what is drawn for it is discarded and the env gets -1), and a player's move -- forward, ``turn_begin``,
+K16's two launches, ``turn_end`` -- is replayed from a captured graph, one per agent index
+(runner/shared/hanabi_turn_graph.py).  A buffer step performs no device -> host copy and no synchronisation; the move,
+game and score counters live in per-table accumulators that ``run()`` reads back once per episode.  The route plays the
+same game of the same policy but NOT the default route's trajectories: the sampler's noise tensor is [N, moves] instead of
+[movers, moves], so from the first move with a table sitting out the same generator state gives different draws -- another
+sample of the same distribution, which is why the flag stays opt-in.  With a policy whose outputs do not depend on the
+batch the routes agree bit for bit (tests/test_hanabi_turns_cpu.py, tests/test_gpu_hanabi_turns.py).  Feed-forward
+policies with the device sampler only; anything else stays on the default device route, with one printed line.
 """
+import os
 import time
 
 import numpy as np
@@ -89,6 +103,25 @@ class HanabiRunner(Runner):
         super(HanabiRunner, self).__init__(config)
         self.true_total_num_steps = 0
         self._device_env = bool(getattr(self.envs, "device_resident", False))
+        self._device_turns = self._device_env and bool(getattr(self.all_args, "use_device_turns", False))
+        if self._device_turns:
+            why = self._device_turns_refusal()
+            if why:
+                print("device turns: %s; the rollout stays on the default device route" % why)
+                self._device_turns = False
+        self.turn_graphs = None
+
+    def _device_turns_refusal(self):
+        """Why this runner cannot take the host-free route (None: it can)."""
+        from onpolicy.algorithms.utils import distributions
+        args, space = self.all_args, self.envs.action_space[0]
+        if getattr(args, "use_recurrent_policy", False) or getattr(args, "use_naive_recurrent_policy", False):
+            return "a recurrent policy carries per-table state through the moves"
+        if distributions.SAMPLING_RNG != "device":
+            return "--sampler_rng host draws on the CPU generator"
+        if space.__class__.__name__ != "Discrete" or space.n > 64 or os.environ.get("MAPPO_FUSED_SAMPLE", "1") == "0":
+            return "the action head is not one the device sampler (K14) takes"
+        return None
 
     def begin_rollout(self):
         """Turn state, staging area and the first deal: what run() sets up before its first buffer step."""
@@ -96,6 +129,9 @@ class HanabiRunner(Runner):
         self._stage = _HostStage(self.buffer.device)
         self.scores = []
         self.warmup()
+        if self._device_turns:
+            from onpolicy.runner.shared import hanabi_turn_graph
+            self.turn_graphs = hanabi_turn_graph.build(self)
 
     def run(self):
         self.begin_rollout()
@@ -108,8 +144,11 @@ class HanabiRunner(Runner):
             if self.use_linear_lr_decay:
                 self.trainer.policy.lr_decay(episode, episodes)
             self.scores = []
+            if self._device_turns:
+                self.turn_ops.begin_episode()
             for step in range(T):
-                self.reset_choose = np.zeros(self.n_rollout_threads, dtype=bool)
+                if not self._device_turns:      # (device turns: a device mask, cleared by insert_and_restart)
+                    self.reset_choose = np.zeros(self.n_rollout_threads, dtype=bool)
                 self.collect(step)
 
                 if step == 0 and episode > 0:
@@ -136,12 +175,17 @@ class HanabiRunner(Runner):
                               episode, episodes, total_num_steps, self.num_env_steps,
                               int(total_num_steps / (end - start))))
                 if self.env_name == "Hanabi":
-                    average_score = np.mean(self.scores) if len(self.scores) > 0 else 0.0
+                    if self._device_turns:
+                        average_score = self.read_turn_counters()["average_score"]
+                    else:
+                        average_score = np.mean(self.scores) if len(self.scores) > 0 else 0.0
                     print("average score is {}.".format(average_score))
                     self._log_scalar('average_score', average_score, self.true_total_num_steps)
                 train_infos["average_step_rewards"] = float(b.rewards.mean())
                 self.log_train(train_infos, self.true_total_num_steps)
             if episode % self.eval_interval == 0 and self.use_eval:
+                if self._device_turns:
+                    self.read_turn_counters()
                 self.eval(self.true_total_num_steps)
 
     def insert_and_restart(self):
@@ -150,6 +194,8 @@ class HanabiRunner(Runner):
         b.chooseinsert(turn.share_obs, turn.obs, turn.rnn_states, turn.rnn_states_critic, turn.actions,
                        turn.action_log_probs, turn.values, turn.rewards, turn.masks, turn.bad_masks,
                        turn.active_masks, turn.available_actions)
+        if self._device_turns:
+            return self._restart_device_turns()
         obs, share_obs, available_actions = self.envs.reset(self.reset_choose)
         share_obs = share_obs if self.use_centralized_V else obs
         rc = self.reset_choose
@@ -167,7 +213,59 @@ class HanabiRunner(Runner):
             self.use_available_actions[rows] = a_d
             self.avail_host[rc] = available_actions[rc]
 
+    def _restart_device_turns(self):
+        """New games on the tables ``turn_end`` marked (a device mask: always, whether or not any is set), their rows merged
+        into the static current rows in place, ``can_move`` from the reset's flags, the marks cleared.  Reads nothing back."""
+        from onpolicy.runner.shared import hanabi_turns
+        o = self.turn_ops
+        obs, share_obs, available_actions, flags = self.envs.reset_device(o.reset_choose)
+        hanabi_turns.merge_restarted(o, obs, share_obs if self.use_centralized_V else obs, available_actions, flags)
+
+    def _warmup_device_turns(self):
+        """The static current rows are the tensors the env's step writes; the first deal is a restart of every table."""
+        from onpolicy.runner.shared import hanabi_turns
+        e = self.envs
+        self.use_obs, self.use_available_actions = e.step_obs, e.step_available_actions
+        self.use_share_obs = e.step_share_obs if self.use_centralized_V else e.step_obs
+        self.turn_ops = o = hanabi_turns.TurnOperands(self.turn, self.use_obs, self.use_share_obs, self.use_available_actions)
+        self.reset_choose = o.reset_choose
+        o.reset_choose.fill_(1)
+        self._restart_device_turns()
+
+    def read_turn_counters(self):
+        """The one readback of the route, once per episode: moves / finished games / their scores / refused moves, summed
+        over the tables -> {"games", "score_sum", "average_score"}; ``true_total_num_steps`` is brought up to date."""
+        c = self.turn_ops.read_counters()
+        if c["refused"].any():
+            raise ValueError("mappo_hanabi_step: illegal move on table %d (or the table was never reset); that table is "
+                             "unchanged, the other tables have advanced" % int(np.flatnonzero(c["refused"])[0]))
+        self.true_total_num_steps = int(c["moves"].sum())
+        games, score_sum = int(c["games"].sum()), int(c["score_sum"].sum())
+        return {"games": games, "score_sum": score_sum, "average_score": score_sum / games if games else 0.0}
+
+    @torch.no_grad()
+    def _collect_device_turns(self, step):
+        """One buffer step of the host-free route: A moves, each a graph replay or the same launches eagerly."""
+        from onpolicy.runner.shared import hanabi_turns
+        if self.turn_graphs is not None:
+            return self.turn_graphs.buffer_step()
+        self.trainer.prep_rollout()
+        for agent_id in range(self.num_agents):
+            self._device_turn_move(agent_id, hanabi_turns)
+
+    def _device_turn_move(self, agent_id, hanabi_turns):
+        """Forward on all N rows, ``turn_begin``, the env step, ``turn_end``: launches only (what the graphs capture)."""
+        turn, o, e = self.turn, self.turn_ops, self.envs
+        value, action, action_log_prob, _, _ = self.trainer.policy.get_actions(
+            self.use_share_obs, self.use_obs, turn.rnn_states[:, agent_id], turn.rnn_states_critic[:, agent_id],
+            turn.masks[:, agent_id], self.use_available_actions)
+        hanabi_turns.turn_begin(o, agent_id, value, action, action_log_prob)
+        e.step_device(o.env_actions)
+        hanabi_turns.turn_end(o, agent_id, e.step_flags, e.step_rewards)
+
     def warmup(self):
+        if self._device_turns:
+            return self._warmup_device_turns()
         self.reset_choose = np.ones(self.n_rollout_threads, dtype=bool)
         obs, share_obs, available_actions = self.envs.reset(self.reset_choose)
         share_obs = share_obs if self.use_centralized_V else obs
@@ -196,6 +294,8 @@ class HanabiRunner(Runner):
 
     @torch.no_grad()
     def collect(self, step):
+        if self._device_turns:
+            return self._collect_device_turns(step)
         turn, n, A = self.turn, self.n_rollout_threads, self.num_agents
         dev = self.buffer.device
         for agent_id in range(A):

@@ -1,0 +1,202 @@
+"""The turn bookkeeping of a Hanabi move without the host ("device turns", ``train_hanabi_forward.py --use_device_turns``).
+
+``HanabiRunner.collect`` (reference onpolicy/runner/shared/hanabi_runner_forward.py:138-220) decides on the host who moves
+and which games restart, and updates a dozen arrays shaped like a buffer row with masked assignments.  Everything those
+decisions need is in device memory already -- bit 8 ("some move is legal") and the status byte of the flags word K16 writes
+per table -- so here the same bookkeeping is two operations on tensors, one before the env step and one after it:
+
+  ``turn_begin``  the movers' current rows and the policy's outputs -> slot ``agent`` of the turn tensors; the env's actions
+                  (-1 where a table sits out)
+  ``turn_end``    rewards, masks, finished games, the counters the host used to keep (moves, finished games, their scores)
+                  and who can move next
+
+For HIP tensors each is ONE launch of libmappo_hip.so (K17: csrc/mappo_turn.hip, ``mappo_hanabi_turn_begin`` / ``_end``).
+On any other device -- and on the GPU with ``MAPPO_TURN_KERNELS=0`` -- the same thing is done with framework ops: that form
+is the specification the kernels are tested against bit for bit (tests/test_gpu_hanabi_turns.py), and it lets the route's
+logic run without a GPU (tests/test_hanabi_turns_cpu.py).  Neither form reads anything back.
+
+``merge_restarted`` is the per-buffer-step counterpart: the rows of the games ``reset`` just dealt go into the static
+current rows in place, and ``can_move`` follows the reset's flags.  It runs once per buffer step, as framework ops.
+"""
+import ctypes
+import os
+
+import torch
+
+from onpolicy import _native
+
+STATUS_RUNNING, STATUS_FINISHED, STATUS_REFUSED = 0, 1, 255
+ROW_FIELDS = ("obs", "share_obs", "available_actions")
+SCALAR_FIELDS = ("values", "actions", "action_log_probs", "rewards", "rewards_since_last_action", "masks", "active_masks")
+
+
+class TurnOperands(object):
+    """Everything a move of the route reads and writes besides the policy's and the env's outputs: the turn tensors
+    (``turn``: a ``_TurnState``, [N, A, W] each), the static current rows [N, W] and the route's own state [N]."""
+
+    COUNTERS = (("moves", torch.int64), ("games", torch.int32), ("score_sum", torch.int32), ("refused", torch.uint8))
+
+    def __init__(self, turn, use_obs, use_share_obs, use_available_actions):
+        self.turn = turn
+        self.use_obs, self.use_share_obs, self.use_available_actions = use_obs, use_share_obs, use_available_actions
+        n, dev = use_obs.shape[0], use_obs.device
+        self.n, self.players, self.device = n, turn.obs.shape[1], dev
+        self.can_move = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.reset_choose = torch.zeros(n, dtype=torch.uint8, device=dev)
+        self.env_actions = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        # the per-table accumulators share one allocation: the host reads them back in ONE copy (``read_counters``)
+        sizes = [n * torch.empty((), dtype=dt).element_size() for _, dt in self.COUNTERS]
+        self._counters = torch.zeros(sum(sizes), dtype=torch.uint8, device=dev)
+        at = 0
+        for (name, dt), size in zip(self.COUNTERS, sizes):
+            setattr(self, name, self._counters[at:at + size].view(dt))
+            at += size
+        self._desc = None
+
+    def state_tensors(self):
+        """What a move changes in place besides the env's own tensors (a graph capture saves and restores these)."""
+        t = self.turn
+        return [getattr(t, k) for k in ROW_FIELDS + SCALAR_FIELDS] + \
+            [self.use_available_actions, self.can_move, self.reset_choose, self.env_actions, self._counters]
+
+    def begin_episode(self):
+        """The score list of the host route starts empty every episode: so do the finished games and their scores."""
+        self.games.zero_()
+        self.score_sum.zero_()
+
+    def read_counters(self):
+        """ONE device -> host copy -> {"moves", "games", "score_sum", "refused"} as numpy arrays [N]."""
+        host = self._counters.cpu().numpy()
+        out, at = {}, 0
+        for name, dt in self.COUNTERS:
+            size = self.n * torch.empty((), dtype=dt).element_size()
+            out[name] = host[at:at + size].view(torch.empty((), dtype=dt).numpy().dtype)
+            at += size
+        return out
+
+
+def use_kernels(tensor):
+    return tensor.is_cuda and os.environ.get("MAPPO_TURN_KERNELS", "1") != "0"
+
+
+# ---------------------------------------------------------------------------------------------- K17
+def _flat(t, n, dtype, what):
+    if t.dtype != dtype or t.numel() != n:
+        raise ValueError("%s: expected %d values of %s, got %s of %s" % (what, n, dtype, tuple(t.shape), t.dtype))
+    return t.contiguous()
+
+
+def descriptor(o):
+    """The ``mappo_hanabi_turn`` of ``o`` with every static pointer filled in (built and checked once)."""
+    if o._desc is None:
+        t, n, A = o.turn, o.n, o.players
+        d = _native.HanabiTurn()
+        for name, use in zip(ROW_FIELDS, (o.use_obs, o.use_share_obs, o.use_available_actions)):
+            field = getattr(t, name)
+            w = use.shape[1]
+            if tuple(field.shape) != (n, A, w) or tuple(use.shape) != (n, w):
+                raise ValueError("turn tensor %s %s does not match its current rows %s" % (name, tuple(field.shape), tuple(use.shape)))
+            for x in (field, use):
+                if x.dtype != torch.float32 or not x.is_contiguous() or x.device != o.device:
+                    raise ValueError("%s: K17 takes contiguous float32 tensors on one device" % name)
+            setattr(d, name, field.data_ptr())
+            setattr(d, "use_" + name, use.data_ptr())
+        for name in SCALAR_FIELDS:
+            field = getattr(t, name)
+            if tuple(field.shape) != (n, A, 1) or field.dtype != torch.float32 or not field.is_contiguous():
+                raise ValueError("turn tensor %s: expected contiguous float32 %s, got %s" % (name, (n, A, 1), tuple(field.shape)))
+            setattr(d, name, field.data_ptr())
+        for name in ("can_move", "reset_choose", "env_actions", "moves", "games", "score_sum", "refused"):
+            setattr(d, name, getattr(o, name).data_ptr())
+        d.n_tables, d.players = n, A
+        d.obs_w, d.share_w, d.avail_w = o.use_obs.shape[1], o.use_share_obs.shape[1], o.use_available_actions.shape[1]
+        o._desc = d
+    return o._desc
+
+
+def _launch(o, entry, agent, **dynamic):
+    d = descriptor(o)
+    keep = []
+    for name, (t, dtype) in dynamic.items():
+        t = _flat(t, o.n, dtype, name)
+        keep.append(t)
+        setattr(d, name, t.data_ptr())
+    with torch.cuda.device(o.device):
+        _native.check(getattr(_native.lib(), entry)(ctypes.byref(d), int(agent), _native.stream_of(o.device)), entry)
+
+
+# ---------------------------------------------------------------------------------------- the two operations
+@torch.no_grad()
+def turn_begin(o, agent, value, action, logp):
+    """Before the env step of player ``agent``'s move.  value / action (int64) / logp: the policy's outputs on ALL N
+    rows ([N, 1]); what it drew for a table that sits out is discarded."""
+    if use_kernels(o.can_move):
+        return _launch(o, "mappo_hanabi_turn_begin", agent, value=(value, torch.float32), action=(action, torch.int64),
+                       logp=(logp, torch.float32))
+    t, n = o.turn, o.n
+    m = o.can_move != 0
+    mc = m.view(n, 1)
+    act = action.reshape(n)
+    o.env_actions.copy_(torch.where(m, act.to(torch.int32), torch.full_like(o.env_actions, -1)))
+    for name, use in zip(ROW_FIELDS, (o.use_obs, o.use_share_obs, o.use_available_actions)):
+        slot = getattr(t, name)[:, agent]
+        slot.copy_(torch.where(mc, use, slot))
+    for slot, new in ((t.values[:, agent], value), (t.actions[:, agent], act), (t.action_log_probs[:, agent], logp)):
+        slot.copy_(torch.where(mc, new.reshape(n, 1).to(torch.float32), slot))
+
+
+@torch.no_grad()
+def turn_end(o, agent, flags, rewards_env):
+    """After the env step.  flags [N] int32: K16's words of that step; rewards_env [N]: its rewards.  ``o.can_move`` still
+    holds what ``turn_begin`` read; it leaves with who can move next."""
+    if use_kernels(o.can_move):
+        return _launch(o, "mappo_hanabi_turn_end", agent, flags=(flags, torch.int32), rewards_env=(rewards_env, torch.float32))
+    t, n, A = o.turn, o.n, o.players
+    flags = flags.reshape(n)
+    m = o.can_move != 0
+    mc = m.view(n, 1)
+    status = flags & 0xff
+    done, alive = status == STATUS_FINISHED, status == STATUS_RUNNING
+    dc, d3 = done.view(n, 1), done.view(n, 1, 1)
+    rsla = t.rewards_since_last_action
+    zero, one = torch.zeros_like(rsla[:, agent]), torch.ones_like(rsla[:, agent])
+    # the acting player collects what accumulated since its previous move; everybody accrues the new reward
+    t.rewards[:, agent] = torch.where(mc, rsla[:, agent], t.rewards[:, agent])
+    rsla[:, agent] = torch.where(mc, zero, rsla[:, agent])
+    rsla.copy_(torch.where(m.view(n, 1, 1), rsla + rewards_env.reshape(n, 1, 1), rsla))
+    o.moves.add_(m.to(torch.int64))
+    # running games: the current player stays live
+    t.masks[:, agent] = torch.where(alive.view(n, 1), one, t.masks[:, agent])
+    t.active_masks[:, agent] = torch.where(alive.view(n, 1), one, t.active_masks[:, agent])
+    # finished games: flagged for restart and counted; nobody may act, players after the current one are inactive
+    o.reset_choose.copy_(torch.where(done, torch.ones_like(o.reset_choose), o.reset_choose))
+    o.games.add_(done.to(torch.int32))
+    o.score_sum.add_(torch.where(done, flags >> 16, torch.zeros_like(flags)))
+    o.use_available_actions.masked_fill_(dc, 0.0)
+    t.masks.masked_fill_(d3, 0.0)
+    t.active_masks[:, agent] = torch.where(dc, one, t.active_masks[:, agent])
+    if agent + 1 < A:
+        rest = slice(agent + 1, A)
+        t.active_masks[:, rest] = torch.where(d3, torch.zeros_like(t.active_masks[:, rest]), t.active_masks[:, rest])
+        t.rewards[:, rest] = torch.where(d3, rsla[:, rest], t.rewards[:, rest])
+        rsla[:, rest] = torch.where(d3, torch.zeros_like(rsla[:, rest]), rsla[:, rest])
+        t.values[:, rest] = torch.where(d3, torch.zeros_like(t.values[:, rest]), t.values[:, rest])
+        t.obs[:, rest] = torch.where(d3, torch.zeros_like(t.obs[:, rest]), t.obs[:, rest])
+        t.share_obs[:, rest] = torch.where(d3, torch.zeros_like(t.share_obs[:, rest]), t.share_obs[:, rest])
+    o.refused.copy_(torch.where(status == STATUS_REFUSED, torch.ones_like(o.refused), o.refused))
+    o.can_move.copy_(torch.where(done, torch.zeros_like(flags), (flags >> 8) & 1))
+
+
+@torch.no_grad()
+def merge_restarted(o, obs, share_obs, available_actions, flags):
+    """Once per buffer step, after ``reset`` on the tables ``o.reset_choose`` marks: their new rows (the reset's tensors)
+    replace the old ones in the static current rows, they can move as the reset's flags say, and the marks are cleared."""
+    n = o.n
+    rc = o.reset_choose != 0
+    rcc = rc.view(n, 1)
+    torch.where(rcc, obs, o.use_obs, out=o.use_obs)
+    if o.use_share_obs.data_ptr() != o.use_obs.data_ptr():
+        torch.where(rcc, share_obs, o.use_share_obs, out=o.use_share_obs)
+    torch.where(rcc, available_actions, o.use_available_actions, out=o.use_available_actions)
+    torch.where(rc, (flags.reshape(n) >> 8) & 1, o.can_move, out=o.can_move)
+    o.reset_choose.zero_()

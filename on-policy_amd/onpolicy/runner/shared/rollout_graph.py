@@ -56,6 +56,9 @@ class RolloutGraph(object):
         else:       # feed-forward policies: the buffer's zero view serves every step
             self.cur_rnn_a, self.cur_rnn_c = b.rnn_states[0], b.rnn_states_critic[0]
         self.side = torch.cuda.Stream(device=dev)      # the critic's branch of the captured step
+        self._init_head(runner)
+
+    def _init_head(self, runner):
         # A PopArt value head REBINDS its weight / bias storage on every update (algorithms/utils/popart.py: the running
         # minibatch's backward still needs the old tensors), so the addresses a capture bakes in would go stale with the first
         # train().  The graph therefore reads static copies of the head, refreshed at the start of every episode.
@@ -105,7 +108,9 @@ class RolloutGraph(object):
 
     def _env_state(self):
         e = self.envs
-        return {k: getattr(e, k).clone() for k in self._state_names()}, e.rng.get_state(), \
+        # (an env without ``rng`` keeps its generators inside its state tensors: the Hanabi tables, K16)
+        rng = getattr(e, "rng", None)
+        return {k: getattr(e, k).clone() for k in self._state_names()}, None if rng is None else rng.get_state(), \
             torch.cuda.get_rng_state(self.dev)
 
     def _carried(self):
@@ -139,7 +144,8 @@ class RolloutGraph(object):
         state, env_rng, dev_rng = snap
         for k, v in state.items():
             getattr(e, k).copy_(v)
-        e.rng.set_state(env_rng)
+        if env_rng is not None:
+            e.rng.set_state(env_rng)
         torch.cuda.set_rng_state(dev_rng, self.dev)
 
     def capture(self):
@@ -163,7 +169,8 @@ class RolloutGraph(object):
                 torch.cuda.current_stream(dev).wait_stream(side)
                 torch.cuda.synchronize(dev)
                 graph = torch.cuda.CUDAGraph()
-                graph.register_generator_state(self.envs.rng)
+                if getattr(self.envs, "rng", None) is not None:
+                    graph.register_generator_state(self.envs.rng)
                 with capturing(graph):
                     self.out, self.infos = self._body()
                 torch.cuda.synchronize(dev)

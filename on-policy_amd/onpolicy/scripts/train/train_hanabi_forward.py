@@ -6,6 +6,12 @@ call (``HanabiBatchVecEnv``).  ``--use_subproc_envs`` builds the reference's lay
 per thread behind ``ChooseSubprocVecEnv`` / ``ChooseDummyVecEnv``; both give identical games for the same seeds.
 ``--use_device_env`` keeps the TRAINING tables in device memory instead (``HanabiDeviceVecEnv``: HIP stepper and encoder,
 same games again); evaluation stays on the host stepper.
+``--use_device_turns`` (with ``--use_device_env``; opt-in) also takes the turn bookkeeping off the host: who moves and which
+games restart are read off the tables' flags words on the device (K17), the policy runs on all N rows, and a player's move is
+replayed from a captured graph -- a buffer step copies nothing to the host.  Same game, same policy, but NOT the default
+route's trajectories: the sampler's noise tensor is [N, moves] instead of [movers, moves], so the same generator state gives
+different draws as soon as one table sits a move out (another sample of the same distribution; see
+runner/shared/hanabi_runner_forward.py).
 
     python -m onpolicy.scripts.train.train_hanabi_forward --env_name Hanabi --hanabi_name Hanabi-Full --num_agents 2 ...
 """
@@ -56,12 +62,17 @@ def parse_args(args, parser):
     parser.add_argument('--use_device_env', action='store_true', default=argparse.SUPPRESS,
                         help="keep the training tables on the GPU (HIP stepper and encoder); evaluation stays on the "
                              "host stepper")
+    parser.add_argument('--use_device_turns', action='store_true', default=argparse.SUPPRESS,
+                        help="with --use_device_env: turn bookkeeping on the GPU too (no device -> host copy per move, "
+                             "moves replayed from captured graphs); samples other trajectories than the default route")
     return parser.parse_known_args(args)[0]
 
 
 def main(args):
     all_args = _launch.apply_algorithm_flags(parse_args(args, get_config()), ("rmappo", "mappo", "ippo"))
     all_args.use_device_env = bool(getattr(all_args, "use_device_env", False))
+    if getattr(all_args, "use_device_turns", False) and not all_args.use_device_env:
+        raise NotImplementedError("--use_device_turns needs --use_device_env (it drives the tables in device memory)")
     device = _launch.device_of(all_args)
     if all_args.use_device_env and all_args.use_subproc_envs:
         raise NotImplementedError("--use_device_env and --use_subproc_envs are two different env layouts: pick one")

@@ -1,0 +1,134 @@
+"""TEST INFRASTRUCTURE shared by tests/test_hanabi_turns_cpu.py and tests/test_gpu_hanabi_turns.py: the stub policy whose
+outputs do not depend on the batch, the adapter that gives the host stepper the device env's host-free contract, and the
+loop that drives ``HanabiRunner`` like ``run()`` does between two updates."""
+import numpy as np
+import torch
+
+from onpolicy.envs.hanabi import batch as hb
+
+BUFFER_FIELDS = ("share_obs", "obs", "rnn_states", "rnn_states_critic", "value_preds", "returns", "actions",
+                 "action_log_probs", "rewards", "masks", "bad_masks", "active_masks", "available_actions")
+T, N = 8, 7
+SEEDS = [3 + 1000 * i for i in range(N)]
+
+
+def stub_get_actions(cent_obs, obs, rnn_states_actor, rnn_states_critic, masks, available_actions=None,
+                     deterministic=False):
+    """action = the lowest legal move (0 for a row without one); value and log-prob are elementwise functions of that
+    index and of single observation entries: equal rows give equal bits whatever else is in the batch."""
+    legal = available_actions > 0
+    rows, moves = legal.shape
+    lowest = (legal.to(torch.int64).cumsum(1) == 0).sum(1)          # illegal moves in front of the first legal one
+    idx = torch.where(lowest < moves, lowest, torch.zeros_like(lowest))
+    f = idx.to(torch.float32).view(rows, 1)
+    value = f * 0.125 + obs[:, 1:2] * 0.5 - cent_obs[:, 0:1] * 0.25
+    logp = -(f + 1.0) * 0.0625 - obs[:, 2:3] * 0.5
+    return value, idx.view(rows, 1), logp, rnn_states_actor, rnn_states_critic
+
+
+class HostTablesWithDeviceContract(object):
+    """``HanabiBatchVecEnv`` (the host stepper) behind the host-free contract of ``HanabiDeviceVecEnv``: rows as tensors
+    that every call rewrites in place, a flags word built from status, legal-moves-any and score, ``step_device`` on an
+    int32 action tensor, ``reset_device`` on a mask.  CPU tensors: what lets the route's logic run without a GPU."""
+
+    device_resident = True
+
+    def __init__(self, all_args, seeds):
+        self.host = hb.HanabiBatchVecEnv(all_args, seeds, copy=False)
+        b = self.host.batch
+        self.num_envs, self.players = b.n, b.players
+        self.action_space, self.observation_space = self.host.action_space, self.host.observation_space
+        self.share_observation_space = self.host.share_observation_space
+        rows = lambda: (torch.zeros(b.n, b.obs.shape[1]), torch.zeros(b.n, b.share_obs.shape[1]),       # noqa: E731
+                        torch.zeros(b.n, b.num_moves), torch.full((b.n,), 2, dtype=torch.int32))
+        self.step_obs, self.step_share_obs, self.step_available_actions, self.step_flags = rows()
+        self._reset_rows = rows()
+        self.step_rewards = torch.zeros(b.n)
+        self.moves_with_sitters, self.step_calls = 0, 0
+
+    def _fill(self, out, status):
+        b = self.host.batch
+        for dst, src in zip(out[:3], (b.obs, b.share_obs, b.available_actions)):
+            dst.copy_(torch.from_numpy(src))
+        flags = status.astype(np.int32) | (b.available_actions.any(axis=1).astype(np.int32) << 8) | \
+            (b.scores.astype(np.int32) << 16)
+        out[3].copy_(torch.from_numpy(flags))
+
+    def step_device(self, env_actions):
+        assert env_actions.dtype == torch.int32 and env_actions.shape == (self.num_envs,)
+        b = self.host.batch
+        a = env_actions.numpy().copy()
+        self.step_calls += 1
+        self.moves_with_sitters += int((a == -1).any() and (a != -1).any())
+        b.step(a)
+        b.encode(a != -1)
+        self._fill((self.step_obs, self.step_share_obs, self.step_available_actions, self.step_flags), b.status)
+        self.step_rewards.copy_(torch.from_numpy(b.rewards))
+
+    def reset_device(self, mask):
+        assert mask.dtype == torch.uint8 and mask.shape == (self.num_envs,)
+        b = self.host.batch
+        choose = mask.numpy().astype(bool)
+        b.reset(choose)
+        b.encode(choose)
+        self._fill(self._reset_rows, np.where(choose, 0, 2))
+        return self._reset_rows
+
+    def close(self):
+        self.host.close()
+
+
+def hanabi_args(players, hidden=64, layer_N=1, all_obs=False, episodes=2, **over):
+    from helpers import make_args
+    args = make_args(env_name="Hanabi", episode_length=T, n_rollout_threads=N, num_env_steps=episodes * T * N,
+                     hidden_size=hidden, layer_N=layer_N, ppo_epoch=2, num_mini_batch=1, algorithm_name="mappo",
+                     log_interval=1, use_wandb=False, use_obs_instead_of_state=all_obs, **over)
+    args.hanabi_name, args.num_agents = "Hanabi-Small", players
+    return args
+
+
+def make_runner(args, envs, device, run_dir, stub=True):
+    from onpolicy.runner.shared.hanabi_runner_forward import HanabiRunner
+    torch.manual_seed(1)
+    np.random.seed(1)
+    run_dir.mkdir()
+    runner = HanabiRunner({"all_args": args, "envs": envs, "eval_envs": None, "num_agents": args.num_agents,
+                           "device": device, "run_dir": run_dir})
+    if stub:
+        runner.trainer.policy.get_actions = stub_get_actions
+    return runner
+
+
+def play(runner, steps=T, each_step=None):
+    """``begin_rollout`` then ``steps`` x (collect, insert, restart), as ``run()`` does between two updates.
+    -> {buffer fields, current rows, counters} as numpy / Python values."""
+    runner.begin_rollout()
+    for step in range(steps):
+        if not runner._device_turns:
+            runner.reset_choose = np.zeros(runner.n_rollout_threads, dtype=bool)
+        runner.collect(step)
+        if each_step is not None:
+            each_step(step)
+        runner.insert_and_restart()
+    return outcome(runner)
+
+
+def outcome(runner):
+    np_ = lambda t: t.detach().cpu().numpy()       # noqa: E731
+    out = {k: np_(getattr(runner.buffer, k)).copy() for k in BUFFER_FIELDS}
+    out["use_rows"] = np.concatenate([np_(t).reshape(-1) for t in (runner.use_obs, runner.use_share_obs,
+                                                                  runner.use_available_actions)])
+    if runner._device_turns:
+        c = runner.read_turn_counters()
+        games, mean = c["games"], c["average_score"]
+    else:
+        games, mean = len(runner.scores), float(np.mean(runner.scores)) if runner.scores else 0.0
+    return out, {"moves": runner.true_total_num_steps, "games": games, "mean_score": mean}
+
+
+def assert_same(a, b, what):
+    (fa, ca), (fb, cb) = a, b
+    assert ca == cb, (what, ca, cb)
+    for k in sorted(fa):
+        assert fa[k].shape == fb[k].shape and fa[k].dtype == fb[k].dtype, (what, k)
+        assert np.array_equal(fa[k], fb[k], equal_nan=True), "%s: %s differs" % (what, k)
