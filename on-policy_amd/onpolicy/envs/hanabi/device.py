@@ -6,9 +6,9 @@ launches (apply + deal by one thread per table, encode by one workgroup per tabl
 ``HanabiDeviceVecEnv`` gives them the ``reset(reset_choose)`` / ``step(actions)`` contract of ``HanabiBatchVecEnv``.
 
 What still crosses to the host is one int32 *flags word* per table and move (status | can-move << 8 | score << 16,
-``FLAG_*`` below): the turn-based runner decides on the host who moves and which games restart.  The runner's opt-in
-"device turns" route reads those words on the device instead (K17, runner/shared/hanabi_turns.py) and drives the tables
-through ``HanabiDeviceVecEnv.step_device`` / ``reset_device``, which launch and read nothing back.
+``flag_*`` below): the turn-based runner decides on the host who moves and which games restart.  Its opt-in "device
+turns" route reads those words on the device instead (K17, runner/shared/hanabi_turns.py) and drives the tables through
+``HanabiDeviceVecEnv.step_device`` / ``reset_device``, which launch and read nothing back.
 
 One difference to the host stepper: ``hanabi_batch_step`` validates every move before it applies any, so an illegal move
 leaves ALL tables untouched.  The device step leaves only the offending table untouched (status 255); by the time the
@@ -25,6 +25,8 @@ from onpolicy.envs.hanabi.batch import (SHARE_ALL_PLAYERS, SHARE_OWN_HAND, Rules
 from onpolicy.envs.spaces import Discrete
 
 STATUS_RUNNING, STATUS_FINISHED, STATUS_IDLE, STATUS_REFUSED = 0, 1, 2, 255
+REFUSED_MOVE = ("mappo_hanabi_step: illegal move on table %d (or the table was never reset); that table is unchanged, the "
+                "other tables have advanced")
 
 
 def flag_status(flags):
@@ -129,6 +131,14 @@ class HanabiDeviceBatch(object):
             actions = torch.from_numpy(np.ascontiguousarray(actions, dtype=np.int32).reshape(-1))
         a = actions.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
         assert a.shape[0] == self.n
+        flags = self.read_flags(self._launch_step(a))
+        refused = np.flatnonzero(flag_status(flags) == STATUS_REFUSED)
+        if refused.size:
+            raise ValueError(REFUSED_MOVE % int(refused[0]))
+        return flags
+
+    def _launch_step(self, a):
+        """The two launches of a move on ``a`` ([n] int32, contiguous, on the device) -> the rows they wrote."""
         rows = self.rows
         with torch.cuda.device(self.device):
             _native.check(self._lib.mappo_hanabi_step(
@@ -136,12 +146,7 @@ class HanabiDeviceBatch(object):
                 self.scores.data_ptr(), rows.obs.data_ptr(), rows.share_obs.data_ptr(),
                 rows.available_actions.data_ptr(), rows.to_move.data_ptr(), rows.flags.data_ptr(), self.n,
                 self.share_mode, *(self._rules + (self._stream(),))), "mappo_hanabi_step")
-            flags = self.read_flags(rows)
-        refused = np.flatnonzero(flag_status(flags) == STATUS_REFUSED)
-        if refused.size:
-            raise ValueError("mappo_hanabi_step: illegal move on table %d (or the table was never reset); that table is "
-                             "unchanged, the other tables have advanced" % int(refused[0]))
-        return flags
+        return rows
 
     def encode(self, active=None):
         """Fills obs / share_obs / available_actions / to_move (zero rows where ``active`` is False or the table was
@@ -236,15 +241,10 @@ class HanabiDeviceVecEnv(object):
         """``env_actions`` [n] int32 on the device, taken as it is (-1: the table sits out) -> the two launches of a move.
         Results: ``step_obs`` / ``step_share_obs`` / ``step_available_actions`` / ``step_flags`` / ``step_rewards`` -- the same
         tensors every call.  A refused move shows as status 255 in ``step_flags``; nothing is read back, nothing raised."""
-        b, rows = self.batch, self.batch.rows
+        b = self.batch
         assert env_actions.dtype == torch.int32 and env_actions.shape == (b.n,) and env_actions.is_contiguous() \
             and env_actions.device == b.device
-        with torch.cuda.device(b.device):
-            _native.check(b._lib.mappo_hanabi_step(
-                b._state.data_ptr(), env_actions.data_ptr(), b.rewards.data_ptr(), b.status.data_ptr(),
-                b.scores.data_ptr(), rows.obs.data_ptr(), rows.share_obs.data_ptr(), rows.available_actions.data_ptr(),
-                rows.to_move.data_ptr(), rows.flags.data_ptr(), b.n, b.share_mode, *(b._rules + (b._stream(),))),
-                "mappo_hanabi_step")
+        b._launch_step(env_actions)
 
     def reset_device(self, mask):
         """``mask`` [n] uint8 on the device: new games where it is set -- none where it is all zero; the two launches run

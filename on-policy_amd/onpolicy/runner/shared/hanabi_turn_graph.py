@@ -1,16 +1,14 @@
 """One player's move of the host-free Hanabi route ("device turns") as ONE graph launch, one graph per agent index.
 
-On that route (``train_hanabi_forward.py --use_device_env --use_device_turns``, runner/shared/hanabi_runner_forward.py) a move
-is launches only: the policy's forward on all N rows of the static current-row tensors, K14's draw, ``turn_begin`` (K17), the
-env's apply + deal and encode (K16), ``turn_end`` (K17).  Nothing in it depends on the host, and the move of agent index
-``a`` runs the same kernels on the same addresses every buffer step -- only ``a`` differs between the moves of a buffer
-step, and it is a kernel argument -- so each of the A <= 5 moves is captured once, before the first rollout, with the
-machinery of rollout_graph.py: warm-up on a side stream, ``capturing()``, snapshot and restore of everything the move
-advances (the tables and their generators, the env's row tensors, the turn tensors and the route's state, torch's device
-generator), the pointer-stability check, static copies of a PopArt head, ``captured()``'s fall-back.  Building the graphs
-does not show in the trajectories (tests/test_gpu_hanabi_turns.py compares captured and eager runs bit for bit).
-
-The tables have no ``torch.Generator``: their generators are part of the table state (K16), which the snapshot covers.
+On that route (``hanabi_routes.DeviceTurns``) a move -- ``route.move(a)`` -- is launches only: the policy's forward on all N
+rows of the static current-row tensors, K14's draw, ``turn_begin`` (K17), the env's apply + deal and encode (K16),
+``turn_end`` (K17).  Nothing in it depends on the host, and the move of agent index ``a`` runs the same kernels on the same
+addresses every buffer step (``a`` is a kernel argument), so each of the A <= 5 moves is captured once, before the first
+rollout, with the machinery of rollout_graph.py: warm-up on a side stream, ``capturing()``, snapshot and restore of
+everything the move advances (the tables with their generators -- they have no ``torch.Generator`` -- the env's row
+tensors, the turn tensors and the route's state, torch's device generator), the pointer-stability check, static copies of a
+PopArt head, ``captured()``'s fall-back.  Building the graphs does not show in the trajectories
+(tests/test_gpu_hanabi_turns.py compares captured and eager runs bit for bit).
 
 ``MAPPO_TURN_GRAPH=0`` keeps the route's eager loop; so does a capture that fails, with ``captured()``'s message.
 """
@@ -18,7 +16,7 @@ import os
 
 import torch
 
-from onpolicy.runner.shared import hanabi_turns, rollout_graph
+from onpolicy.runner.shared import rollout_graph
 
 
 class HanabiTurnGraph(rollout_graph.RolloutGraph):
@@ -31,11 +29,11 @@ class HanabiTurnGraph(rollout_graph.RolloutGraph):
 
     @torch.no_grad()
     def _body(self):
-        self.r._device_turn_move(self.agent, hanabi_turns)
+        self.r.route.move(self.agent)
         return None, None
 
     def _carried(self):
-        return self.r.turn_ops.state_tensors()
+        return self.r.route.ops.state_tensors()
 
     def begin_episode(self):
         """Nothing is carried in tensors of the graph's own; a PopArt head is read through static copies, as the last

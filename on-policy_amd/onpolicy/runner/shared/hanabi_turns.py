@@ -1,22 +1,18 @@
-"""The turn bookkeeping of a Hanabi move without the host ("device turns", ``train_hanabi_forward.py --use_device_turns``).
+"""The turn bookkeeping of a Hanabi move (reference onpolicy/runner/shared/hanabi_runner_forward.py:138-220) on tensors.
 
-``HanabiRunner.collect`` (reference onpolicy/runner/shared/hanabi_runner_forward.py:138-220) decides on the host who moves
-and which games restart, and updates a dozen arrays shaped like a buffer row with masked assignments.  Everything those
-decisions need is in device memory already -- bit 8 ("some move is legal") and the status byte of the flags word K16 writes
-per table -- so here the same bookkeeping is two operations on tensors, one before the env step and one after it:
+What follows an env step is the same on every route of ``HanabiRunner`` (runner/shared/hanabi_routes.py) and stands here
+once: ``settle_move`` and ``settle_finished``, on explicit masks.  The host-decided routes call them with what the host saw.
+The host-free route ("device turns", ``--use_device_turns``) reads who moves and which games restart off the flags word K16
+writes per table, so there the whole bookkeeping is two operations, one before the env step and one after it:
 
-  ``turn_begin``  the movers' current rows and the policy's outputs -> slot ``agent`` of the turn tensors; the env's actions
-                  (-1 where a table sits out)
-  ``turn_end``    rewards, masks, finished games, the counters the host used to keep (moves, finished games, their scores)
-                  and who can move next
+  ``turn_begin``  the movers' rows and the policy's outputs -> slot ``agent`` of the turn tensors; the env's actions (-1: sits out)
+  ``turn_end``    the settling, the counters the host used to keep (moves, finished games, their scores), who can move next
 
 For HIP tensors each is ONE launch of libmappo_hip.so (K17: csrc/mappo_turn.hip, ``mappo_hanabi_turn_begin`` / ``_end``).
-On any other device -- and on the GPU with ``MAPPO_TURN_KERNELS=0`` -- the same thing is done with framework ops: that form
-is the specification the kernels are tested against bit for bit (tests/test_gpu_hanabi_turns.py), and it lets the route's
-logic run without a GPU (tests/test_hanabi_turns_cpu.py).  Neither form reads anything back.
-
-``merge_restarted`` is the per-buffer-step counterpart: the rows of the games ``reset`` just dealt go into the static
-current rows in place, and ``can_move`` follows the reset's flags.  It runs once per buffer step, as framework ops.
+On any other device -- and on the GPU with ``MAPPO_TURN_KERNELS=0`` -- the same thing is done with framework ops: the
+specification the kernels are tested against bit for bit (tests/test_gpu_hanabi_turns.py), which also lets the route's
+logic run without a GPU (tests/test_hanabi_turns_cpu.py).  Neither form reads anything back.  ``merge_restarted`` is the
+per-buffer-step counterpart (framework ops): the rows ``reset`` just dealt go into the static current rows in place.
 """
 import ctypes
 import os
@@ -24,8 +20,8 @@ import os
 import torch
 
 from onpolicy import _native
+from onpolicy.envs.hanabi.device import STATUS_FINISHED, STATUS_REFUSED, STATUS_RUNNING, flag_can_move, flag_score, flag_status
 
-STATUS_RUNNING, STATUS_FINISHED, STATUS_REFUSED = 0, 1, 255
 ROW_FIELDS = ("obs", "share_obs", "available_actions")
 SCALAR_FIELDS = ("values", "actions", "action_log_probs", "rewards", "rewards_since_last_action", "masks", "active_masks")
 
@@ -45,12 +41,13 @@ class TurnOperands(object):
         self.reset_choose = torch.zeros(n, dtype=torch.uint8, device=dev)
         self.env_actions = torch.full((n,), -1, dtype=torch.int32, device=dev)
         # the per-table accumulators share one allocation: the host reads them back in ONE copy (``read_counters``)
-        sizes = [n * torch.empty((), dtype=dt).element_size() for _, dt in self.COUNTERS]
-        self._counters = torch.zeros(sum(sizes), dtype=torch.uint8, device=dev)
-        at = 0
-        for (name, dt), size in zip(self.COUNTERS, sizes):
-            setattr(self, name, self._counters[at:at + size].view(dt))
-            at += size
+        self._spans, at = {}, 0
+        for name, dt in self.COUNTERS:
+            self._spans[name] = (at, at + n * torch.empty((), dtype=dt).element_size(), dt)
+            at = self._spans[name][1]
+        self._counters = torch.zeros(at, dtype=torch.uint8, device=dev)
+        for name, (a, b, dt) in self._spans.items():
+            setattr(self, name, self._counters[a:b].view(dt))
         self._desc = None
 
     def state_tensors(self):
@@ -59,20 +56,10 @@ class TurnOperands(object):
         return [getattr(t, k) for k in ROW_FIELDS + SCALAR_FIELDS] + \
             [self.use_available_actions, self.can_move, self.reset_choose, self.env_actions, self._counters]
 
-    def begin_episode(self):
-        """The score list of the host route starts empty every episode: so do the finished games and their scores."""
-        self.games.zero_()
-        self.score_sum.zero_()
-
     def read_counters(self):
         """ONE device -> host copy -> {"moves", "games", "score_sum", "refused"} as numpy arrays [N]."""
-        host = self._counters.cpu().numpy()
-        out, at = {}, 0
-        for name, dt in self.COUNTERS:
-            size = self.n * torch.empty((), dtype=dt).element_size()
-            out[name] = host[at:at + size].view(torch.empty((), dtype=dt).numpy().dtype)
-            at += size
-        return out
+        host = self._counters.cpu()
+        return {name: host[a:b].view(dt).numpy() for name, (a, b, dt) in self._spans.items()}
 
 
 def use_kernels(tensor):
@@ -151,40 +138,59 @@ def turn_end(o, agent, flags, rewards_env):
     holds what ``turn_begin`` read; it leaves with who can move next."""
     if use_kernels(o.can_move):
         return _launch(o, "mappo_hanabi_turn_end", agent, flags=(flags, torch.int32), rewards_env=(rewards_env, torch.float32))
-    t, n, A = o.turn, o.n, o.players
+    t, n = o.turn, o.n
     flags = flags.reshape(n)
     m = o.can_move != 0
-    mc = m.view(n, 1)
-    status = flags & 0xff
-    done, alive = status == STATUS_FINISHED, status == STATUS_RUNNING
-    dc, d3 = done.view(n, 1), done.view(n, 1, 1)
-    rsla = t.rewards_since_last_action
-    zero, one = torch.zeros_like(rsla[:, agent]), torch.ones_like(rsla[:, agent])
-    # the acting player collects what accumulated since its previous move; everybody accrues the new reward
-    t.rewards[:, agent] = torch.where(mc, rsla[:, agent], t.rewards[:, agent])
-    rsla[:, agent] = torch.where(mc, zero, rsla[:, agent])
-    rsla.copy_(torch.where(m.view(n, 1, 1), rsla + rewards_env.reshape(n, 1, 1), rsla))
+    status = flag_status(flags)
+    done = status == STATUS_FINISHED
+    settle_move(t, agent, m, status == STATUS_RUNNING, rewards_env)
+    settle_finished(t, agent, done, o.use_available_actions)
+    # what the host used to keep: moves, games flagged for restart and counted, refused moves, who can move next
     o.moves.add_(m.to(torch.int64))
-    # running games: the current player stays live
-    t.masks[:, agent] = torch.where(alive.view(n, 1), one, t.masks[:, agent])
-    t.active_masks[:, agent] = torch.where(alive.view(n, 1), one, t.active_masks[:, agent])
-    # finished games: flagged for restart and counted; nobody may act, players after the current one are inactive
     o.reset_choose.copy_(torch.where(done, torch.ones_like(o.reset_choose), o.reset_choose))
     o.games.add_(done.to(torch.int32))
-    o.score_sum.add_(torch.where(done, flags >> 16, torch.zeros_like(flags)))
-    o.use_available_actions.masked_fill_(dc, 0.0)
+    o.score_sum.add_(torch.where(done, flag_score(flags), torch.zeros_like(flags)))
+    o.refused.copy_(torch.where(status == STATUS_REFUSED, torch.ones_like(o.refused), o.refused))
+    o.can_move.copy_(torch.where(done, torch.zeros_like(flags), flag_can_move(flags)))
+
+
+@torch.no_grad()
+def settle_move(turn, agent, moved, alive, rewards):
+    """The acting player collects what accumulated since its previous move and everybody at a table that moved accrues the
+    new reward (the reward of buffer step 0 is discarded by the shift in ``run()``); in running games the current player
+    stays live.  moved: bool [N] on the device, or None for "every table"; alive: bool [N]; rewards: [N] or [N, A, 1]."""
+    rsla = turn.rewards_since_last_action
+    n = rsla.shape[0]
+    rewards = rewards.reshape(n, -1, 1)
+    if moved is None:
+        turn.rewards[:, agent] = rsla[:, agent]
+        rsla[:, agent] = 0.0
+        rsla += rewards
+    else:
+        mc = moved.view(n, 1)
+        turn.rewards[:, agent] = torch.where(mc, rsla[:, agent], turn.rewards[:, agent])
+        rsla[:, agent] = torch.where(mc, torch.zeros_like(rsla[:, agent]), rsla[:, agent])
+        rsla.copy_(torch.where(moved.view(n, 1, 1), rsla + rewards, rsla))
+    live, one = alive.view(n, 1), torch.ones_like(turn.masks[:, agent])
+    turn.masks[:, agent] = torch.where(live, one, turn.masks[:, agent])
+    turn.active_masks[:, agent] = torch.where(live, one, turn.active_masks[:, agent])
+
+
+@torch.no_grad()
+def settle_finished(turn, agent, done, use_available_actions):
+    """Finished games (done: bool [N]): nobody may act; the current player is active, the players after it are inactive,
+    their accrued rewards are flushed and their values and rows zeroed."""
+    t, rsla = turn, turn.rewards_since_last_action
+    n, A = rsla.shape[:2]
+    dc, d3 = done.view(n, 1), done.view(n, 1, 1)
+    use_available_actions.masked_fill_(dc, 0.0)
     t.masks.masked_fill_(d3, 0.0)
-    t.active_masks[:, agent] = torch.where(dc, one, t.active_masks[:, agent])
+    t.active_masks[:, agent] = torch.where(dc, torch.ones_like(t.active_masks[:, agent]), t.active_masks[:, agent])
     if agent + 1 < A:
         rest = slice(agent + 1, A)
-        t.active_masks[:, rest] = torch.where(d3, torch.zeros_like(t.active_masks[:, rest]), t.active_masks[:, rest])
         t.rewards[:, rest] = torch.where(d3, rsla[:, rest], t.rewards[:, rest])
-        rsla[:, rest] = torch.where(d3, torch.zeros_like(rsla[:, rest]), rsla[:, rest])
-        t.values[:, rest] = torch.where(d3, torch.zeros_like(t.values[:, rest]), t.values[:, rest])
-        t.obs[:, rest] = torch.where(d3, torch.zeros_like(t.obs[:, rest]), t.obs[:, rest])
-        t.share_obs[:, rest] = torch.where(d3, torch.zeros_like(t.share_obs[:, rest]), t.share_obs[:, rest])
-    o.refused.copy_(torch.where(status == STATUS_REFUSED, torch.ones_like(o.refused), o.refused))
-    o.can_move.copy_(torch.where(done, torch.zeros_like(flags), (flags >> 8) & 1))
+        for field in (t.active_masks, rsla, t.values, t.obs, t.share_obs):
+            field[:, rest] = torch.where(d3, torch.zeros_like(field[:, rest]), field[:, rest])
 
 
 @torch.no_grad()
@@ -198,5 +204,5 @@ def merge_restarted(o, obs, share_obs, available_actions, flags):
     if o.use_share_obs.data_ptr() != o.use_obs.data_ptr():
         torch.where(rcc, share_obs, o.use_share_obs, out=o.use_share_obs)
     torch.where(rcc, available_actions, o.use_available_actions, out=o.use_available_actions)
-    torch.where(rc, (flags.reshape(n) >> 8) & 1, o.can_move, out=o.can_move)
+    torch.where(rc, flag_can_move(flags.reshape(n)), o.can_move, out=o.can_move)
     o.reset_choose.zero_()

@@ -104,8 +104,6 @@ def play(runner, steps=T, each_step=None):
     -> {buffer fields, current rows, counters} as numpy / Python values."""
     runner.begin_rollout()
     for step in range(steps):
-        if not runner._device_turns:
-            runner.reset_choose = np.zeros(runner.n_rollout_threads, dtype=bool)
         runner.collect(step)
         if each_step is not None:
             each_step(step)
@@ -118,12 +116,16 @@ def outcome(runner):
     out = {k: np_(getattr(runner.buffer, k)).copy() for k in BUFFER_FIELDS}
     out["use_rows"] = np.concatenate([np_(t).reshape(-1) for t in (runner.use_obs, runner.use_share_obs,
                                                                   runner.use_available_actions)])
-    if runner._device_turns:
-        c = runner.read_turn_counters()
-        games, mean = c["games"], c["average_score"]
-    else:
-        games, mean = len(runner.scores), float(np.mean(runner.scores)) if runner.scores else 0.0
-    return out, {"moves": runner.true_total_num_steps, "games": games, "mean_score": mean}
+    c = runner.route.score_summary()
+    return out, {"moves": runner.true_total_num_steps, "games": c["games"], "mean_score": float(c["average_score"])}
+
+
+def recorded(gold, players):
+    """The host-tables route as commit 184a686 played it (tools/make_golden_hanabi_routes.py), in ``outcome``'s form: the
+    anchor that shares no code with the routes."""
+    z, key = gold.npz("hanabi_route_cases"), "a%d_" % players
+    fields = {k: z[key + k] for k in BUFFER_FIELDS + ("use_rows",)}
+    return fields, {"moves": int(z[key + "moves"]), "games": int(z[key + "games"]), "mean_score": float(z[key + "mean_score"])}
 
 
 def assert_same(a, b, what):

@@ -168,15 +168,18 @@ def _device_runner(tmp_path, tag, turns, stub, players=2, **arg_over):
     return common.make_runner(args, envs, DEV, tmp_path / tag, stub=stub)
 
 
-def test_three_routes_agree_with_a_batch_independent_policy(tmp_path, monkeypatch):
+def test_three_routes_agree_with_a_batch_independent_policy(tmp_path, monkeypatch, gold):
     """Default device route, device turns eager, device turns captured, all with the CPU test's stub policy (lowest legal
-    move): buffers, current rows, move / game counters and the mean score bit-identical."""
+    move): buffers, current rows, move / game counters and the mean score bit-identical -- with each other and with the
+    recording of the host-tables route on the CPU (tests/golden/hanabi_route_cases.npz: the stub's arithmetic is exact
+    and elementwise, so CPU and GPU agree)."""
     default = common.play(_device_runner(tmp_path, "default", False, True))
     assert default[1]["games"] >= 20
+    common.assert_same(common.recorded(gold, 2), default, "recorded host-tables route (CPU) vs default device route")
     monkeypatch.setenv("MAPPO_TURN_GRAPH", "0")
     runner = _device_runner(tmp_path, "eager", True, True)
     eager = common.play(runner)
-    assert runner._device_turns and runner.turn_graphs is None
+    assert runner.route.name == "device_turns" and runner.turn_graphs is None
     monkeypatch.setenv("MAPPO_TURN_GRAPH", "1")
     runner = _device_runner(tmp_path, "captured", True, True)
     captured = common.play(runner)
@@ -277,7 +280,7 @@ def test_train_script_with_device_turns(tmp_path, monkeypatch):
     for graph in ("1", "0"):
         monkeypatch.setenv("MAPPO_TURN_GRAPH", graph)
         runner = train_hanabi_forward.main(argv)
-        assert runner._device_turns and (runner.turn_graphs is not None) == (graph == "1")
+        assert runner.route.name == "device_turns" and (runner.turn_graphs is not None) == (graph == "1")
         assert type(runner.envs).__name__ == "HanabiDeviceVecEnv" and type(runner.eval_envs).__name__ == "HanabiBatchVecEnv"
         assert runner.true_total_num_steps > 0
         logged = [json.loads(l) for l in open(os.path.join(runner.log_dir, "scalars.jsonl"))]

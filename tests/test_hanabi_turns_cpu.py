@@ -26,13 +26,14 @@ def host_buffer(monkeypatch):
 
 
 @pytest.mark.parametrize("players", [2, 3])
-def test_device_turns_route_equals_default_route_on_host_tables(host_buffer, tmp_path, players):
+def test_device_turns_route_equals_default_route_on_host_tables(host_buffer, tmp_path, gold, players):
     """Hanabi-Small, N = 7, T = 8: the default route on ``HanabiBatchVecEnv`` and the eager device-turns route on the same
     stepper behind the device env's contract, both with the stub policy (lowest legal move): every buffer field, the
     current rows, the move count, the number of finished games and the mean score are bit-identical.  The stub loses its
     one life quickly, so the ground is covered -- asserted below; on the host stepper with these seeds: A = 2: 52 finished
     games, 6 moves with a table sitting out, 2 buffer steps in which every table had finished before the last player's
-    move; A = 3: 55 / 10 / 5."""
+    move; A = 3: 55 / 10 / 5.  Both outcomes also equal, bit for bit, the recording of the host-tables route made before the
+    routes came to share their bookkeeping (tests/golden/hanabi_route_cases.npz)."""
     args = common.hanabi_args(players)
     host_envs = hb.HanabiBatchVecEnv(args, common.SEEDS, copy=False)
     step, seen = host_envs.step, {"sitters": 0, "calls": 0}
@@ -44,7 +45,7 @@ def test_device_turns_route_equals_default_route_on_host_tables(host_buffer, tmp
         return step(actions)
     host_envs.step = counting_step
     default = common.make_runner(args, host_envs, CPU, tmp_path / "default")
-    assert not default._device_turns
+    assert default.route.name == "host_tables"
     calls_per_step = []
     expected = common.play(default, each_step=lambda s: calls_per_step.append(seen["calls"]))
     all_out = sum(1 for a, b in zip([0] + calls_per_step, calls_per_step) if b - a < players)
@@ -52,16 +53,18 @@ def test_device_turns_route_equals_default_route_on_host_tables(host_buffer, tmp
           % (players, expected[1]["games"], seen["sitters"], all_out))
     assert expected[1]["games"] >= 20 and seen["sitters"] >= 3 and all_out >= 1
     assert expected[1]["moves"] > 0
+    common.assert_same(common.recorded(gold, players), expected, "recorded host-tables route vs default route")
 
     turn_args = common.hanabi_args(players)
     turn_args.use_device_turns = True
     envs = common.HostTablesWithDeviceContract(turn_args, common.SEEDS)
     turns = common.make_runner(turn_args, envs, CPU, tmp_path / "turns")
-    assert turns._device_turns and turns.turn_graphs is None
+    assert turns.route.name == "device_turns" and turns.turn_graphs is None
     got = common.play(turns)
     assert turns.turn_graphs is None            # a CPU device: the eager loop
     assert envs.step_calls == common.T * players and envs.moves_with_sitters == seen["sitters"]
     common.assert_same(expected, got, "device turns (eager, CPU) vs default route")
+    common.assert_same(common.recorded(gold, players), got, "recorded host-tables route vs device turns (eager, CPU)")
     host_envs.close()
     envs.close()
 
@@ -154,9 +157,9 @@ def test_recurrent_policy_stays_on_the_default_device_route(host_buffer, tmp_pat
     runner = common.make_runner(args, envs, CPU, tmp_path / "rnn", stub=False)
     lines = [l for l in capsys.readouterr().out.splitlines() if "device turns" in l]
     assert len(lines) == 1 and "recurrent" in lines[0] and "default device route" in lines[0]
-    assert runner._device_env and not runner._device_turns
+    assert runner.route.name == "device_tables"
     # ... and the flag with a feed-forward policy takes the route
     args = common.hanabi_args(2)
     args.use_device_turns = True
-    assert common.make_runner(args, envs, CPU, tmp_path / "mlp")._device_turns
+    assert common.make_runner(args, envs, CPU, tmp_path / "mlp").route.name == "device_turns"
     envs.close()

@@ -61,22 +61,18 @@ def build_runner(shape, way, steps):
                            "device": device, "run_dir": pathlib.Path(tempfile.mkdtemp())})
     os.environ["MAPPO_TURN_GRAPH"] = "1" if way == "captured" else "0"      # read when begin_rollout builds the graphs
     runner.begin_rollout()
-    assert runner._device_turns == (way != "default") and (runner.turn_graphs is not None) == (way == "captured")
+    assert (runner.route.name == "device_turns") == (way != "default") and (runner.turn_graphs is not None) == (way == "captured")
     return runner
 
 
 def collect_phase(runner, steps):
-    import numpy as np
     for step in range(steps):
-        if not runner._device_turns:
-            runner.reset_choose = np.zeros(runner.n_rollout_threads, dtype=bool)
         runner.collect(step)
         runner.insert_and_restart()
 
 
 def moves_so_far(runner):
-    if runner._device_turns:
-        runner.read_turn_counters()
+    runner.route.score_summary()
     return runner.true_total_num_steps
 
 

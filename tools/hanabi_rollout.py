@@ -70,9 +70,7 @@ def build_runner(shape, on_device, steps):
 
 
 def collect_phase(runner, steps):
-    import numpy as np
     for step in range(steps):
-        runner.reset_choose = np.zeros(runner.n_rollout_threads, dtype=bool)
         runner.collect(step)
         runner.insert_and_restart()
 
