@@ -981,6 +981,53 @@ typedef struct mappo_hanabi_turn {
 int mappo_hanabi_turn_begin(const mappo_hanabi_turn_t* args, int agent, mappo_stream_t stream);
 int mappo_hanabi_turn_end(const mappo_hanabi_turn_t* args, int agent, mappo_stream_t stream);
 
+/* ------------------------------------------------- K18: the bookkeeping of a Hanabi EVALUATION move, from the flags words ----
+ * What HanabiRunner.eval does around the env step of one player's move (reference
+ * onpolicy/runner/shared/hanabi_runner_forward.py:229 onwards: the choose mask, the -1 actions of the tables that sit out,
+ * eval_rnn_states[choose, agent_id] = ..., eval_available_actions[eval_dones == True] = 0, the eval_scores list) as two
+ * launches in K17's shape that read "who moves" and "which games ended" off device memory, so that an evaluation move needs
+ * no device -> host copy.  Evaluation bookkeeping is not training bookkeeping: no buffer slots, rewards or masks; per-table
+ * final scores; RNN state carried per (table, player) through a whole game; finished tables are never restarted.
+ *   current rows [n_tables, avail_w] float32: use_available_actions;
+ *   rnn_states [n_tables, players, rnn_w] float32 (rnn_w = recurrent_N * hidden), rnn_new [n_tables, rnn_w]: the policy's new
+ *     states on all rows -- BOTH NULL for a feed-forward policy (rnn_w is ignored then);
+ *   the policy's action [n_tables] int64; the env's flags [n_tables] int32 (K16);
+ *   the route's state [n_tables]: can_move, env_actions (int32), and the per-table counters moves (int64), games, scores
+ *     (int32), refused (uint8).
+ * use_available_actions, rnn_states and rnn_new must be 16-byte aligned, moves and action 8-byte, the others 4-byte.
+ *
+ * mappo_hanabi_eval_begin(agent), per table n with m = can_move[n] != 0:
+ *   env_actions[n] = m ? (int32) action[n] : -1;  if m and the RNN pointers are set: rnn_states[n, agent, :] = rnn_new[n, :].
+ *   A table that sits out keeps its state: what the policy computed for it is discarded.
+ * mappo_hanabi_eval_end(agent), per table n with f = flags[n], status = f & 0xff, m as eval_begin read it:
+ *   if m:                 moves[n] += 1
+ *   if m and status == 1: scores[n] = f >> 16; games[n] += 1; row n of use_available_actions = 0
+ *   if status == 255:     refused[n] = 1 (sticky)
+ *   can_move[n] = (m && status == 0) ? (f >> 8) & 1 : 0
+ * A finished table is counted once and never moves again (K16 reports it as status 2 with zero rows from then on).
+ * MAPPO_E_NULL (a pointer the call reads or writes; the other call's may be NULL; one RNN pointer without the other),
+ * MAPPO_E_SHAPE (n_tables <= 0, players outside [1, 5], agent outside [0, players), avail_w <= 0, rnn_w <= 0 with the RNN
+ * pointers set) and MAPPO_E_ALIGN are returned before anything is enqueued. */
+typedef struct mappo_hanabi_eval {
+    float* use_available_actions;
+    float* rnn_states;
+    const float* rnn_new;
+    const int64_t* action;
+    const int32_t* flags;
+    int32_t* can_move;
+    int32_t* env_actions;
+    int64_t* moves;
+    int32_t* games;
+    int32_t* scores;
+    uint8_t* refused;
+    int64_t n_tables;
+    int32_t players;
+    int32_t avail_w;
+    int32_t rnn_w;
+} mappo_hanabi_eval_t;
+int mappo_hanabi_eval_begin(const mappo_hanabi_eval_t* args, int agent, mappo_stream_t stream);
+int mappo_hanabi_eval_end(const mappo_hanabi_eval_t* args, int agent, mappo_stream_t stream);
+
 /* --------------------------------------------------------------------- misc ---- */
 int         mappo_abi_version(void);
 const char* mappo_build_info(void);        /* "gfx950 ..." static string */

@@ -10,6 +10,10 @@
 // are written as aligned float4 between a scalar head and a scalar tail (the idiom of stream_row in mappo_hanabi.hip), and
 // read as float4 too when the source row sits at the same offset from a 16-byte boundary as the destination row (else as
 // four dwords: still consecutive lanes on consecutive addresses).  No LDS, no atomics, nothing allocated.
+//
+// K18: the same two launches for an EVALUATION move (include/mappo_hip.h, "K18"): no buffer slots, rewards or masks, but the
+// actor's RNN state per (table, player), a final score per table, and finished tables that never restart.  Same shape, same
+// row helpers.
 #include "mappo_internal.h"
 #include "../../include/mappo_hip.h"
 
@@ -122,6 +126,42 @@ __global__ void __launch_bounds__(kThreads) hanabi_turn_end_kernel(mappo_hanabi_
     }
 }
 
+__global__ void __launch_bounds__(kThreads) hanabi_eval_begin_kernel(mappo_hanabi_eval_t d, int agent) {
+    const int lane = threadIdx.x & 63;
+    const long long first = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6), step = (long long)gridDim.x * kWaves;
+    const size_t A = (size_t)d.players;
+    for (long long n = first; n < d.n_tables; n += step) {
+        const bool m = d.can_move[n] != 0;           // one address per wave
+        if (lane == 0) d.env_actions[n] = m ? (int32_t)d.action[n] : -1;
+        if (!m || !d.rnn_states) continue;
+        copy_row(d.rnn_states, ((size_t)n * A + (size_t)agent) * d.rnn_w, d.rnn_new, (size_t)n * d.rnn_w, d.rnn_w, lane);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) hanabi_eval_end_kernel(mappo_hanabi_eval_t d, int agent) {
+    const int lane = threadIdx.x & 63;
+    const long long first = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6), step = (long long)gridDim.x * kWaves;
+    for (long long n = first; n < d.n_tables; n += step) {
+        const int32_t f = d.flags[n];
+        const int status = f & 0xff;
+        // can_move[n] is read and rewritten by lane 0 alone; whether the table just finished reaches the other lanes
+        // (which clear its legal-move row) from lane 0's registers, not through memory
+        const bool m = lane == 0 && d.can_move[n] != 0;
+        const bool done = m && status == kStatusDone;
+        const bool done_u = __shfl((int)done, 0) != 0;
+        if (lane == 0) {
+            if (m) d.moves[n] += 1;
+            if (done) {
+                d.scores[n] = f >> 16;
+                d.games[n] += 1;
+            }
+            if (status == kStatusRefused) d.refused[n] = 1;
+            d.can_move[n] = (m && status == 0) ? (f >> 8) & 1 : 0;
+        }
+        if (done_u) zero_row(d.use_available_actions, (size_t)n * d.avail_w, d.avail_w, lane);
+    }
+}
+
 // `used`: the pointers this entry point reads or writes (the other one's may be NULL).
 template <size_t K>
 int check(const mappo_hanabi_turn_t* d, int agent, const void* const (&used)[K]) {
@@ -137,6 +177,24 @@ int check(const mappo_hanabi_turn_t* d, int agent, const void* const (&used)[K])
     const void* words[] = {d->values, d->actions, d->action_log_probs, d->rewards, d->rewards_since_last_action, d->masks,
                            d->active_masks, d->value, d->logp, d->flags, d->rewards_env, d->can_move, d->env_actions,
                            d->games, d->score_sum};
+    for (const void* p : words)
+        if (!mappo::aligned_to(p, 4)) return MAPPO_E_ALIGN;
+    return 0;
+}
+
+template <size_t K>
+int check_eval(const mappo_hanabi_eval_t* d, int agent, const void* const (&used)[K]) {
+    for (const void* p : used)
+        if (!p) return MAPPO_E_NULL;
+    if ((d->rnn_states == nullptr) != (d->rnn_new == nullptr)) return MAPPO_E_NULL;
+    if (d->n_tables <= 0 || d->players < 1 || d->players > MAPPO_TURN_MAX_PLAYERS || agent < 0 || agent >= d->players ||
+        d->avail_w <= 0 || (d->rnn_states && d->rnn_w <= 0))
+        return MAPPO_E_SHAPE;
+    const void* rows[] = {d->use_available_actions, d->rnn_states, d->rnn_new};
+    for (const void* p : rows)
+        if (!mappo::aligned_to(p, 16)) return MAPPO_E_ALIGN;
+    if (!mappo::aligned_to(d->moves, 8) || !mappo::aligned_to(d->action, 8)) return MAPPO_E_ALIGN;
+    const void* words[] = {d->flags, d->can_move, d->env_actions, d->games, d->scores};
     for (const void* p : words)
         if (!mappo::aligned_to(p, 4)) return MAPPO_E_ALIGN;
     return 0;
@@ -171,6 +229,28 @@ extern "C" int mappo_hanabi_turn_end(const mappo_hanabi_turn_t* args, int agent,
     const int rc = check(args, agent, used);
     if (rc != 0) return rc;
     hipLaunchKernelGGL(hanabi_turn_end_kernel, dim3(grid_of(args->n_tables)), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream_), *args, agent);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mappo_hanabi_eval_begin(const mappo_hanabi_eval_t* args, int agent, mappo_stream_t stream_) {
+    if (!args) return MAPPO_E_NULL;
+    const mappo_hanabi_eval_t& d = *args;
+    const void* const used[] = {d.action, d.can_move, d.env_actions};
+    const int rc = check_eval(args, agent, used);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(hanabi_eval_begin_kernel, dim3(grid_of(args->n_tables)), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream_), *args, agent);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mappo_hanabi_eval_end(const mappo_hanabi_eval_t* args, int agent, mappo_stream_t stream_) {
+    if (!args) return MAPPO_E_NULL;
+    const mappo_hanabi_eval_t& d = *args;
+    const void* const used[] = {d.use_available_actions, d.flags, d.can_move, d.moves, d.games, d.scores, d.refused};
+    const int rc = check_eval(args, agent, used);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(hanabi_eval_end_kernel, dim3(grid_of(args->n_tables)), dim3(kThreads), 0,
                        static_cast<hipStream_t>(stream_), *args, agent);
     return (int)hipGetLastError();
 }

@@ -130,6 +130,13 @@ class HanabiTurn(ctypes.Structure):
                [("n_tables", _i64)] + [(n, ctypes.c_int32) for n in ("players", "obs_w", "share_w", "avail_w")]
 
 
+class HanabiEval(ctypes.Structure):
+    """struct mappo_hanabi_eval (include/mappo_hip.h): every operand of K18's two launches."""
+    _fields_ = [(n, _vp) for n in ("use_available_actions", "rnn_states", "rnn_new", "action", "flags", "can_move",
+                                   "env_actions", "moves", "games", "scores", "refused")] + \
+               [("n_tables", _i64)] + [(n, ctypes.c_int32) for n in ("players", "avail_w", "rnn_w")]
+
+
 LOSS_HUBER, LOSS_CLIPPED_VALUE, LOSS_POLICY_ACTIVE_MASKS, LOSS_VALUE_ACTIVE_MASKS = 1, 2, 4, 8
 
 _RULES = [ctypes.c_int32] * 8
@@ -225,6 +232,9 @@ SIGNATURES = {
     # K17
     "mappo_hanabi_turn_begin": (_int, [ctypes.POINTER(HanabiTurn), _int, _vp]),
     "mappo_hanabi_turn_end": (_int, [ctypes.POINTER(HanabiTurn), _int, _vp]),
+    # K18
+    "mappo_hanabi_eval_begin": (_int, [ctypes.POINTER(HanabiEval), _int, _vp]),
+    "mappo_hanabi_eval_end": (_int, [ctypes.POINTER(HanabiEval), _int, _vp]),
     "mappo_abi_version": (_int, []),
     "mappo_build_info": (ctypes.c_char_p, []),
     "mappo_error_string": (ctypes.c_char_p, [_int]),

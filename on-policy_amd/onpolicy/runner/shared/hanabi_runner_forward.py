@@ -8,6 +8,8 @@ buffer field, [N, A, ...]): ``chooseinsert`` is a device-to-device slab write (K
 (reference :59-63) device copies, ``compute`` / ``train`` the GAE kernel and the fused update.  How a buffer step's A
 moves are played is the business of ``self.route``, chosen once in ``__init__`` (runner/shared/hanabi_routes.py: host
 tables, device tables, device turns); what follows an env step stands once, in runner/shared/hanabi_turns.py.
+Evaluation plays on the host stepper move by move (``_eval_games``) or, with ``--use_device_eval``, on device-resident eval
+tables without the host (runner/shared/hanabi_eval.py: K18, captured moves).
 """
 import os
 import time
@@ -49,6 +51,11 @@ class HanabiRunner(Runner):
                 else:
                     route = hanabi_routes.DeviceTurns
         self.route = route(self)
+        # opt-in (--use_device_eval): the evaluation plays on device-resident eval tables without the host (hanabi_eval.py)
+        self.device_eval = None
+        if getattr(self.all_args, "use_device_eval", False) and getattr(self.eval_envs, "device_resident", False):
+            from onpolicy.runner.shared import hanabi_eval
+            self.device_eval = hanabi_eval.DeviceEval(self)
 
     def _device_turns_refusal(self):
         """Why this runner cannot take the host-free route (None: it can)."""
@@ -146,7 +153,10 @@ class HanabiRunner(Runner):
 
     @torch.no_grad()
     def _eval_games(self):
-        """Play the eval envs to the end with the deterministic policy -> list of final scores."""
+        """Play the eval envs to the end with the deterministic policy -> list of final scores (with ``--use_device_eval``:
+        an array, one score per table, from the device route)."""
+        if self.device_eval is not None:
+            return self.device_eval.games()
         n, envs = self.n_eval_rollout_threads, self.eval_envs
         scores = []
         obs, share_obs, available_actions = envs.reset(np.ones(n, dtype=bool))

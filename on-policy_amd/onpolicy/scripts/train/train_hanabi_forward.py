@@ -5,7 +5,11 @@ The env is the in-tree batched stepper (``onpolicy.envs.hanabi``): all rollout t
 call (``HanabiBatchVecEnv``).  ``--use_subproc_envs`` builds the reference's layout instead -- one ``HanabiEnv``
 per thread behind ``ChooseSubprocVecEnv`` / ``ChooseDummyVecEnv``; both give identical games for the same seeds.
 ``--use_device_env`` keeps the TRAINING tables in device memory instead (``HanabiDeviceVecEnv``: HIP stepper and encoder,
-same games again); evaluation stays on the host stepper.
+same games again); where the evaluation plays is a flag of its own:
+``--use_device_eval`` (with ``--use_eval``; opt-in, independent of ``--use_device_env``) keeps the EVAL tables in device memory
+and plays an evaluation without the host: the deterministic action (K14 mode), the env step (K16) and the bookkeeping between
+them (K18: runner/shared/hanabi_eval.py) are launches only, a move is replayed from a captured graph, and the host reads one
+block of counters every few rounds.  Without it evaluation runs on the host stepper, move by move.
 ``--use_device_turns`` (with ``--use_device_env``; opt-in) also takes the turn bookkeeping off the host: who moves and which
 games restart are read off the tables' flags words on the device (K17), the policy runs on all N rows, and a player's move is
 replayed from a captured graph -- a buffer step copies nothing to the host.  Same game, same policy, but NOT the default
@@ -24,7 +28,8 @@ from onpolicy.scripts.train import _launch
 
 
 def make_env(all_args, n_threads, seed_of_rank, device=None):
-    """``device``: build the tables in that device's memory (the training envs under ``--use_device_env``)."""
+    """``device``: build the tables in that device's memory (the training envs under ``--use_device_env``, the eval envs
+    under ``--use_device_eval``)."""
     if all_args.env_name != "Hanabi":
         raise NotImplementedError("Can not support the " + all_args.env_name + " environment.")
     assert 1 < all_args.num_agents < 6, "num_agents can be only between 2-5."
@@ -60,12 +65,28 @@ def parse_args(args, parser):
     # opt-in and absent from the namespace unless given (main() reads it as False then): a run without it parses
     # exactly as before
     parser.add_argument('--use_device_env', action='store_true', default=argparse.SUPPRESS,
-                        help="keep the training tables on the GPU (HIP stepper and encoder); evaluation stays on the "
-                             "host stepper")
+                        help="keep the training tables on the GPU (HIP stepper and encoder); the eval tables follow "
+                             "--use_device_eval")
     parser.add_argument('--use_device_turns', action='store_true', default=argparse.SUPPRESS,
                         help="with --use_device_env: turn bookkeeping on the GPU too (no device -> host copy per move, "
                              "moves replayed from captured graphs); samples other trajectories than the default route")
+    parser.add_argument('--use_device_eval', action='store_true', default=argparse.SUPPRESS,
+                        help="with --use_eval: keep the EVAL tables on the GPU and play the evaluation without the host "
+                             "(K18, captured moves); independent of --use_device_env")
     return parser.parse_known_args(args)[0]
+
+
+def check_device_eval(all_args, device=None):
+    """-> whether ``--use_device_eval`` was given; refuses the combinations it cannot serve (``device``: once it is known)."""
+    if not getattr(all_args, "use_device_eval", False):
+        return False
+    if not all_args.use_eval:
+        raise NotImplementedError("--use_device_eval needs --use_eval (it only changes how the evaluation is played)")
+    if all_args.use_subproc_envs:
+        raise NotImplementedError("--use_device_eval and --use_subproc_envs are two different env layouts: pick one")
+    if device is not None and device.type != "cuda":
+        raise NotImplementedError("--use_device_eval needs a GPU device (the eval tables live in its memory)")
+    return True
 
 
 def main(args):
@@ -73,7 +94,9 @@ def main(args):
     all_args.use_device_env = bool(getattr(all_args, "use_device_env", False))
     if getattr(all_args, "use_device_turns", False) and not all_args.use_device_env:
         raise NotImplementedError("--use_device_turns needs --use_device_env (it drives the tables in device memory)")
+    check_device_eval(all_args)
     device = _launch.device_of(all_args)
+    device_eval = check_device_eval(all_args, device)
     if all_args.use_device_env and all_args.use_subproc_envs:
         raise NotImplementedError("--use_device_env and --use_subproc_envs are two different env layouts: pick one")
     if all_args.use_device_env and device.type != "cuda":
@@ -83,7 +106,8 @@ def main(args):
     envs = make_env(all_args, all_args.n_rollout_threads, lambda rank: all_args.seed + (getattr(all_args, "rollout_thread_offset", 0) + rank) * 1000,
                     device=device if all_args.use_device_env else None)
     eval_envs = make_env(all_args, all_args.n_eval_rollout_threads,
-                         lambda rank: all_args.seed * 50000 + rank * 10000) if all_args.use_eval else None
+                         lambda rank: all_args.seed * 50000 + rank * 10000,
+                         device=device if device_eval else None) if all_args.use_eval else None
     if not all_args.share_policy:
         raise NotImplementedError("the separated Hanabi runner is outside this implementation")
     from onpolicy.runner.shared.hanabi_runner_forward import HanabiRunner as Runner
