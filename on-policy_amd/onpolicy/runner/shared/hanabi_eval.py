@@ -18,10 +18,9 @@ run without a GPU (tests/test_hanabi_eval_cpu.py).  Neither form reads anything 
 ``DeviceEval`` is the route: ``HanabiRunner._eval_games`` hands over to its ``games()`` when the eval envs are device tables
 and the flag is given.  A move -- the actor's forward on ALL N rows, its deterministic action (K14 mode), ``eval_begin``, the
 env's two launches (K16), ``eval_end`` -- is launches only, and is replayed from a captured graph, one per agent index
-(hanabi_eval_graph.py).  The host reads ONE block of counters every ``MAPPO_HANABI_EVAL_POLL`` rounds of A moves and stops
+(hanabi_moves.py).  The host reads ONE block of counters every ``MAPPO_HANABI_EVAL_POLL`` rounds of A moves and stops
 when every table has finished.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -29,15 +28,15 @@ import torch
 
 from onpolicy import _native
 from onpolicy.envs.hanabi.batch import rules_for
-from onpolicy.envs.hanabi.device import (REFUSED_MOVE, STATUS_FINISHED, STATUS_REFUSED, STATUS_RUNNING, flag_can_move,
-                                         flag_score, flag_status)
-from onpolicy.runner.shared.hanabi_turns import _flat, use_kernels
+from onpolicy.envs.hanabi.device import STATUS_FINISHED, STATUS_REFUSED, STATUS_RUNNING, flag_can_move, flag_score, flag_status
+from onpolicy.runner.shared import eval_graph, hanabi_moves
+from onpolicy.runner.shared.hanabi_moves import launch, use_kernels
 
 # rounds of A moves between two reads of the counter block (``MAPPO_HANABI_EVAL_POLL``)
 DEFAULT_POLL = 4
 
 
-class EvalOperands(object):
+class EvalOperands(hanabi_moves.MoveOperands):
     """Everything an evaluation move reads and writes besides the policy's and the env's outputs: the static current rows
     [N, W], who can move and the env's actions [N], the actor's RNN states [N, A, recurrent_N, hidden] and the per-table
     counters."""
@@ -45,47 +44,28 @@ class EvalOperands(object):
     COUNTERS = (("moves", torch.int64), ("games", torch.int32), ("scores", torch.int32), ("refused", torch.uint8))
 
     def __init__(self, use_obs, use_available_actions, players, recurrent_N, hidden, recurrent):
-        self.use_obs, self.use_available_actions = use_obs, use_available_actions
-        n, dev = use_obs.shape[0], use_obs.device
-        self.n, self.players, self.device, self.recurrent = n, int(players), dev, bool(recurrent)
-        self.can_move = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.env_actions = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        super(EvalOperands, self).__init__(use_obs.shape[0], players, use_obs.device)
+        self.use_obs, self.use_available_actions, self.recurrent = use_obs, use_available_actions, bool(recurrent)
+        f32 = dict(dtype=torch.float32, device=self.device)
         # (feed-forward policies hand the states back as they got them: these stay zero)
-        self.rnn_states = torch.zeros(n, self.players, recurrent_N, hidden, dtype=torch.float32, device=dev)
-        self.masks = torch.ones(n, 1, dtype=torch.float32, device=dev)
-        # the per-table counters share one allocation: the host reads them back in ONE copy (``read_counters``)
-        self._spans, at = {}, 0
-        for name, dt in self.COUNTERS:
-            self._spans[name] = (at, at + n * torch.empty((), dtype=dt).element_size(), dt)
-            at = self._spans[name][1]
-        self._counters = torch.zeros(at, dtype=torch.uint8, device=dev)
-        for name, (a, b, dt) in self._spans.items():
-            setattr(self, name, self._counters[a:b].view(dt))
-        self._desc = None
+        self.rnn_states = torch.zeros(self.n, self.players, recurrent_N, hidden, **f32)
+        self.masks = torch.ones(self.n, 1, **f32)
 
     def begin(self, flags):
         """The state an evaluation starts from; ``flags``: the words of the reset just made."""
         self.can_move.copy_(flag_can_move(flags.reshape(self.n)))
         self.env_actions.fill_(-1)
         self.rnn_states.zero_()
-        self._counters.zero_()
+        self.counter_block.zero_()
         self.scores.fill_(-1)
 
     def state_tensors(self):
         """What a move changes in place besides the env's own tensors (a graph capture saves and restores these)."""
-        return [self.use_available_actions, self.can_move, self.env_actions, self.rnn_states, self._counters]
+        return [self.use_available_actions, self.can_move, self.env_actions, self.rnn_states, self.counter_block]
 
-    def read_counters(self):
-        """ONE device -> host copy -> {"moves", "games", "scores", "refused"} as numpy arrays [N]."""
-        host = self._counters.cpu()
-        return {name: host[a:b].view(dt).numpy() for name, (a, b, dt) in self._spans.items()}
-
-
-# ---------------------------------------------------------------------------------------------- K18
-def descriptor(o):
-    """The ``mappo_hanabi_eval`` of ``o`` with every static pointer filled in (built and checked once)."""
-    if o._desc is None:
-        avail, rnn = o.use_available_actions, o.rnn_states
+    def _describe(self):
+        """The ``mappo_hanabi_eval`` (K18) of these operands: the legal-move rows and the carried RNN states."""
+        o, avail, rnn = self, self.use_available_actions, self.rnn_states
         for name, x in (("use_available_actions", avail), ("rnn_states", rnn)):
             if x.dtype != torch.float32 or not x.is_contiguous() or x.device != o.device:
                 raise ValueError("%s: K18 takes contiguous float32 tensors on one device" % name)
@@ -95,23 +75,8 @@ def descriptor(o):
         d = _native.HanabiEval()
         d.use_available_actions = avail.data_ptr()
         d.rnn_states = rnn.data_ptr() if o.recurrent else None
-        for name in ("can_move", "env_actions", "moves", "games", "scores", "refused"):
-            setattr(d, name, getattr(o, name).data_ptr())
-        d.n_tables, d.players, d.avail_w = o.n, o.players, avail.shape[1]
-        d.rnn_w = rnn.shape[2] * rnn.shape[3]
-        o._desc = d
-    return o._desc
-
-
-def _launch(o, entry, agent, **dynamic):
-    d = descriptor(o)
-    keep = []
-    for name, (t, numel, dtype) in dynamic.items():
-        t = _flat(t, numel, dtype, name)
-        keep.append(t)
-        setattr(d, name, t.data_ptr())
-    with torch.cuda.device(o.device):
-        _native.check(getattr(_native.lib(), entry)(ctypes.byref(d), int(agent), _native.stream_of(o.device)), entry)
+        d.avail_w, d.rnn_w = avail.shape[1], rnn.shape[2] * rnn.shape[3]
+        return d
 
 
 # ---------------------------------------------------------------------------------------- the two operations
@@ -123,7 +88,7 @@ def eval_begin(o, agent, action, rnn_new):
         dynamic = dict(action=(action, o.n, torch.int64))
         if o.recurrent:
             dynamic["rnn_new"] = (rnn_new, o.rnn_states[:, agent].numel(), torch.float32)
-        return _launch(o, "mappo_hanabi_eval_begin", agent, **dynamic)
+        return launch(o, "mappo_hanabi_eval_begin", agent, **dynamic)
     n = o.n
     m = o.can_move != 0
     o.env_actions.copy_(torch.where(m, action.reshape(n).to(torch.int32), torch.full_like(o.env_actions, -1)))
@@ -137,7 +102,7 @@ def eval_end(o, agent, flags):
     """After the env step.  flags [N] int32: K16's words of that step.  ``o.can_move`` still holds what ``eval_begin`` read;
     it leaves with who can move next.  A finished table is counted once and never moves again."""
     if use_kernels(o.can_move):
-        return _launch(o, "mappo_hanabi_eval_end", agent, flags=(flags, o.n, torch.int32))
+        return launch(o, "mappo_hanabi_eval_end", agent, flags=(flags, o.n, torch.int32))
     n = o.n
     flags = flags.reshape(n)
     m = o.can_move != 0
@@ -204,17 +169,16 @@ class DeviceEval(object):
     def _poll(self):
         self.readbacks += 1
         c = self.counters = self.ops.read_counters()
-        if c["refused"].any():
-            raise ValueError(REFUSED_MOVE % int(np.flatnonzero(c["refused"])[0]))
+        hanabi_moves.raise_if_refused(c)
         return bool((c["games"] > 0).all())
 
     @torch.no_grad()
     def games(self):
-        from onpolicy.runner.shared import hanabi_eval_graph
         self.r.trainer.prep_rollout()
         self._begin()
         if not hasattr(self, "graphs"):         # tried once per runner, on the first evaluation
-            self.graphs = hanabi_eval_graph.build(self)
+            self.graphs = hanabi_moves.build(self.r, self, self.envs, self.n, self.r.device, with_value_head=False,
+                                             enabled=eval_graph.enabled(), what="Hanabi eval move")
         poll = poll_rounds()
         self.rounds, self.readbacks = 0, 0
         while True:

@@ -6,11 +6,13 @@ clears its own restart marks), ``restart()`` (new games on the tables ``collect`
 ``score_summary()`` (-> {"games", "average_score"} of the episode so far; ``runner.true_total_num_steps`` up to date) and the
 current rows ``use_obs`` / ``use_share_obs`` / ``use_available_actions``.  All write the turn tensors ``runner.turn``.
 """
+import os
+
 import numpy as np
 import torch
 
-from onpolicy.envs.hanabi.device import REFUSED_MOVE, STATUS_FINISHED, STATUS_RUNNING, flag_status
-from onpolicy.runner.shared import hanabi_turns
+from onpolicy.envs.hanabi.device import STATUS_FINISHED, STATUS_RUNNING, flag_status
+from onpolicy.runner.shared import hanabi_moves, hanabi_turns
 from onpolicy.runner.shared.base_runner import _t2n
 
 
@@ -189,7 +191,7 @@ class DeviceTurns(_Route):
     """Who moves and which games restart are read off the flags words ON the device (K17's two launches around the env
     step), the policy runs on ALL N rows of static current-row tensors (a table that sits out has an all-zero legal-move
     row; what is drawn for it is discarded and the env gets -1), and a move is replayed from a captured graph, one per
-    agent index (hanabi_turn_graph.py).  A buffer step copies nothing to the host and never synchronises: the restart
+    agent index (hanabi_moves.py).  A buffer step copies nothing to the host and never synchronises: the restart
     marks are a device mask that ``restart()`` consumes and clears, the counters per-table accumulators.  NOT the
     host-decided routes' trajectories: the sampler's noise tensor is [N, moves] instead of [movers, moves], so from the
     first move with a table sitting out the same generator state gives other draws (hence opt-in); with a policy whose
@@ -198,14 +200,14 @@ class DeviceTurns(_Route):
 
     def warmup(self):
         """Static current rows: the tensors the env's step writes; the first deal restarts every table; then the capture."""
-        from onpolicy.runner.shared import hanabi_turn_graph
         r, e = self.r, self.r.envs
         self.use_obs, self.use_available_actions = e.step_obs, e.step_available_actions
         self.use_share_obs = e.step_share_obs if r.use_centralized_V else e.step_obs
         self.ops = hanabi_turns.TurnOperands(r.turn, self.use_obs, self.use_share_obs, self.use_available_actions)
         self.ops.reset_choose.fill_(1)
         self.restart()
-        self.turn_graphs = hanabi_turn_graph.build(r)
+        self.turn_graphs = hanabi_moves.build(r, self, e, r.n_rollout_threads, r.buffer.device, with_value_head=True,
+                                              enabled=os.environ.get("MAPPO_TURN_GRAPH", "1") != "0", what="Hanabi move")
 
     def begin_episode(self):
         """The score list of the host-decided routes starts empty every episode: so do the games and their scores."""
@@ -239,8 +241,7 @@ class DeviceTurns(_Route):
     def score_summary(self):
         """The one readback of the route: moves / finished games / their scores / refused moves, summed over the tables."""
         c = self.ops.read_counters()
-        if c["refused"].any():
-            raise ValueError(REFUSED_MOVE % int(np.flatnonzero(c["refused"])[0]))
+        hanabi_moves.raise_if_refused(c)
         self.r.true_total_num_steps = int(c["moves"].sum())
         games, score_sum = int(c["games"].sum()), int(c["score_sum"].sum())
         return {"games": games, "average_score": score_sum / games if games else 0.0}

@@ -14,69 +14,38 @@ specification the kernels are tested against bit for bit (tests/test_gpu_hanabi_
 logic run without a GPU (tests/test_hanabi_turns_cpu.py).  Neither form reads anything back.  ``merge_restarted`` is the
 per-buffer-step counterpart (framework ops): the rows ``reset`` just dealt go into the static current rows in place.
 """
-import ctypes
-import os
-
 import torch
 
 from onpolicy import _native
 from onpolicy.envs.hanabi.device import STATUS_FINISHED, STATUS_REFUSED, STATUS_RUNNING, flag_can_move, flag_score, flag_status
+from onpolicy.runner.shared import hanabi_moves
+from onpolicy.runner.shared.hanabi_moves import launch, use_kernels
 
 ROW_FIELDS = ("obs", "share_obs", "available_actions")
 SCALAR_FIELDS = ("values", "actions", "action_log_probs", "rewards", "rewards_since_last_action", "masks", "active_masks")
 
 
-class TurnOperands(object):
+class TurnOperands(hanabi_moves.MoveOperands):
     """Everything a move of the route reads and writes besides the policy's and the env's outputs: the turn tensors
     (``turn``: a ``_TurnState``, [N, A, W] each), the static current rows [N, W] and the route's own state [N]."""
 
     COUNTERS = (("moves", torch.int64), ("games", torch.int32), ("score_sum", torch.int32), ("refused", torch.uint8))
 
     def __init__(self, turn, use_obs, use_share_obs, use_available_actions):
+        super(TurnOperands, self).__init__(use_obs.shape[0], turn.obs.shape[1], use_obs.device)
         self.turn = turn
         self.use_obs, self.use_share_obs, self.use_available_actions = use_obs, use_share_obs, use_available_actions
-        n, dev = use_obs.shape[0], use_obs.device
-        self.n, self.players, self.device = n, turn.obs.shape[1], dev
-        self.can_move = torch.zeros(n, dtype=torch.int32, device=dev)
-        self.reset_choose = torch.zeros(n, dtype=torch.uint8, device=dev)
-        self.env_actions = torch.full((n,), -1, dtype=torch.int32, device=dev)
-        # the per-table accumulators share one allocation: the host reads them back in ONE copy (``read_counters``)
-        self._spans, at = {}, 0
-        for name, dt in self.COUNTERS:
-            self._spans[name] = (at, at + n * torch.empty((), dtype=dt).element_size(), dt)
-            at = self._spans[name][1]
-        self._counters = torch.zeros(at, dtype=torch.uint8, device=dev)
-        for name, (a, b, dt) in self._spans.items():
-            setattr(self, name, self._counters[a:b].view(dt))
-        self._desc = None
+        self.reset_choose = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
 
     def state_tensors(self):
         """What a move changes in place besides the env's own tensors (a graph capture saves and restores these)."""
         t = self.turn
         return [getattr(t, k) for k in ROW_FIELDS + SCALAR_FIELDS] + \
-            [self.use_available_actions, self.can_move, self.reset_choose, self.env_actions, self._counters]
+            [self.use_available_actions, self.can_move, self.reset_choose, self.env_actions, self.counter_block]
 
-    def read_counters(self):
-        """ONE device -> host copy -> {"moves", "games", "score_sum", "refused"} as numpy arrays [N]."""
-        host = self._counters.cpu()
-        return {name: host[a:b].view(dt).numpy() for name, (a, b, dt) in self._spans.items()}
-
-
-def use_kernels(tensor):
-    return tensor.is_cuda and os.environ.get("MAPPO_TURN_KERNELS", "1") != "0"
-
-
-# ---------------------------------------------------------------------------------------------- K17
-def _flat(t, n, dtype, what):
-    if t.dtype != dtype or t.numel() != n:
-        raise ValueError("%s: expected %d values of %s, got %s of %s" % (what, n, dtype, tuple(t.shape), t.dtype))
-    return t.contiguous()
-
-
-def descriptor(o):
-    """The ``mappo_hanabi_turn`` of ``o`` with every static pointer filled in (built and checked once)."""
-    if o._desc is None:
-        t, n, A = o.turn, o.n, o.players
+    def _describe(self):
+        """The ``mappo_hanabi_turn`` (K17) of these operands: the turn tensors, the current rows and the restart marks."""
+        o, t, n, A = self, self.turn, self.n, self.players
         d = _native.HanabiTurn()
         for name, use in zip(ROW_FIELDS, (o.use_obs, o.use_share_obs, o.use_available_actions)):
             field = getattr(t, name)
@@ -93,23 +62,9 @@ def descriptor(o):
             if tuple(field.shape) != (n, A, 1) or field.dtype != torch.float32 or not field.is_contiguous():
                 raise ValueError("turn tensor %s: expected contiguous float32 %s, got %s" % (name, (n, A, 1), tuple(field.shape)))
             setattr(d, name, field.data_ptr())
-        for name in ("can_move", "reset_choose", "env_actions", "moves", "games", "score_sum", "refused"):
-            setattr(d, name, getattr(o, name).data_ptr())
-        d.n_tables, d.players = n, A
+        d.reset_choose = o.reset_choose.data_ptr()
         d.obs_w, d.share_w, d.avail_w = o.use_obs.shape[1], o.use_share_obs.shape[1], o.use_available_actions.shape[1]
-        o._desc = d
-    return o._desc
-
-
-def _launch(o, entry, agent, **dynamic):
-    d = descriptor(o)
-    keep = []
-    for name, (t, dtype) in dynamic.items():
-        t = _flat(t, o.n, dtype, name)
-        keep.append(t)
-        setattr(d, name, t.data_ptr())
-    with torch.cuda.device(o.device):
-        _native.check(getattr(_native.lib(), entry)(ctypes.byref(d), int(agent), _native.stream_of(o.device)), entry)
+        return d
 
 
 # ---------------------------------------------------------------------------------------- the two operations
@@ -118,8 +73,8 @@ def turn_begin(o, agent, value, action, logp):
     """Before the env step of player ``agent``'s move.  value / action (int64) / logp: the policy's outputs on ALL N
     rows ([N, 1]); what it drew for a table that sits out is discarded."""
     if use_kernels(o.can_move):
-        return _launch(o, "mappo_hanabi_turn_begin", agent, value=(value, torch.float32), action=(action, torch.int64),
-                       logp=(logp, torch.float32))
+        return launch(o, "mappo_hanabi_turn_begin", agent, value=(value, o.n, torch.float32), action=(action, o.n, torch.int64),
+                      logp=(logp, o.n, torch.float32))
     t, n = o.turn, o.n
     m = o.can_move != 0
     mc = m.view(n, 1)
@@ -137,7 +92,8 @@ def turn_end(o, agent, flags, rewards_env):
     """After the env step.  flags [N] int32: K16's words of that step; rewards_env [N]: its rewards.  ``o.can_move`` still
     holds what ``turn_begin`` read; it leaves with who can move next."""
     if use_kernels(o.can_move):
-        return _launch(o, "mappo_hanabi_turn_end", agent, flags=(flags, torch.int32), rewards_env=(rewards_env, torch.float32))
+        return launch(o, "mappo_hanabi_turn_end", agent, flags=(flags, o.n, torch.int32),
+                      rewards_env=(rewards_env, o.n, torch.float32))
     t, n = o.turn, o.n
     flags = flags.reshape(n)
     m = o.can_move != 0

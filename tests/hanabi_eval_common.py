@@ -4,6 +4,8 @@ evaluations on either route.  Shapes, seeds and arguments are those of hanabi_tu
 import numpy as np
 import torch
 
+from onpolicy.envs.hanabi import batch as hb
+
 import hanabi_turns_common as common
 
 N = common.N
@@ -40,12 +42,7 @@ def eval_args(players, device_eval, recurrent=False, **over):
 
 def make_runner(args, envs, eval_envs, device, run_dir, stub=None):
     """``HanabiRunner`` with eval envs; ``stub``: a ``StubAct`` to put in the policy's place."""
-    from onpolicy.runner.shared.hanabi_runner_forward import HanabiRunner
-    torch.manual_seed(1)
-    np.random.seed(1)
-    run_dir.mkdir()
-    runner = HanabiRunner({"all_args": args, "envs": envs, "eval_envs": eval_envs, "num_agents": args.num_agents,
-                           "device": device, "run_dir": run_dir})
+    runner = common.make_runner(args, envs, device, run_dir, stub=False, eval_envs=eval_envs)
     if stub is not None:
         runner.trainer.policy.act = stub
     return runner
@@ -55,7 +52,6 @@ class CountingHostEnvs(object):
     """The host stepper as eval envs, recording which tables moved in every ``step`` (``moved``: bool [N] per call)."""
 
     def __init__(self, args, seeds):
-        from onpolicy.envs.hanabi import batch as hb
         self.host = hb.HanabiBatchVecEnv(args, seeds, copy=False)
         self.moved = []
 
@@ -78,7 +74,6 @@ def host_rnn_states(moved, states, players, shape):
 
 def play_host(run_dir, players, recurrent, device, evaluations=2, stub=True, **over):
     """``evaluations`` x the untouched host ``_eval_games`` on ``HanabiBatchVecEnv`` -> one record per evaluation."""
-    from onpolicy.envs.hanabi import batch as hb
     args = eval_args(players, False, recurrent, **over)
     envs, eval_envs = hb.HanabiBatchVecEnv(args, common.SEEDS, copy=False), CountingHostEnvs(args, EVAL_SEEDS)
     act = StubAct(record=True) if stub else None
@@ -101,7 +96,6 @@ def play_host(run_dir, players, recurrent, device, evaluations=2, stub=True, **o
 
 def play_device(run_dir, players, recurrent, device, eval_envs, evaluations=2, stub=True, each=None, **over):
     """``evaluations`` x ``_eval_games`` with ``--use_device_eval`` on ``eval_envs`` -> (runner, one record per evaluation)."""
-    from onpolicy.envs.hanabi import batch as hb
     args = eval_args(players, True, recurrent, **over)
     envs = hb.HanabiBatchVecEnv(args, common.SEEDS, copy=False)
     runner = make_runner(args, envs, eval_envs, device, run_dir, StubAct() if stub else None)

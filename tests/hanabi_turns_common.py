@@ -1,15 +1,34 @@
-"""TEST INFRASTRUCTURE shared by tests/test_hanabi_turns_cpu.py and tests/test_gpu_hanabi_turns.py: the stub policy whose
-outputs do not depend on the batch, the adapter that gives the host stepper the device env's host-free contract, and the
-loop that drives ``HanabiRunner`` like ``run()`` does between two updates."""
+"""TEST INFRASTRUCTURE shared by the Hanabi runner tests (tests/test_hanabi_{turns,eval}_cpu.py, tests/test_gpu_hanabi_*.py):
+the stub policy whose outputs do not depend on the batch, the adapter that gives the host stepper the device env's host-free
+contract, the loop that drives ``HanabiRunner`` like ``run()`` does between two updates, and what the K17 / K18 tests share:
+fake descriptors, the header-struct parser, bitwise comparison, the grid cap, allocations with canaries."""
+import ctypes
+import os
+import re
+
 import numpy as np
+import pytest
 import torch
 
+from host_buffer import HostSharedBuffer
+from onpolicy import _native
 from onpolicy.envs.hanabi import batch as hb
 
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mappo_hip.h")
+CAP_TABLES = _native.TURN_MAX_BLOCKS * 4        # K17 / K18: one wave per table, four waves a workgroup
 BUFFER_FIELDS = ("share_obs", "obs", "rnn_states", "rnn_states_critic", "value_preds", "returns", "actions",
                  "action_log_probs", "rewards", "masks", "bad_masks", "active_masks", "available_actions")
 T, N = 8, 7
 SEEDS = [3 + 1000 * i for i in range(N)]
+ARGV = ["--env_name", "Hanabi", "--hanabi_name", "Hanabi-Small", "--num_agents", "2", "--algorithm_name", "mappo",
+        "--n_rollout_threads", "7", "--episode_length", "8", "--num_env_steps", "112", "--use_wandb"]      # (the scripts)
+
+
+@pytest.fixture
+def host_buffer(monkeypatch):
+    """Runners on a CPU device: the rollout buffer on host tensors."""
+    import onpolicy.runner.shared.base_runner as base
+    monkeypatch.setattr(base, "SharedReplayBuffer", HostSharedBuffer)
 
 
 def stub_get_actions(cent_obs, obs, rnn_states_actor, rnn_states_critic, masks, available_actions=None,
@@ -87,12 +106,12 @@ def hanabi_args(players, hidden=64, layer_N=1, all_obs=False, episodes=2, **over
     return args
 
 
-def make_runner(args, envs, device, run_dir, stub=True):
+def make_runner(args, envs, device, run_dir, stub=True, eval_envs=None):
     from onpolicy.runner.shared.hanabi_runner_forward import HanabiRunner
     torch.manual_seed(1)
     np.random.seed(1)
     run_dir.mkdir()
-    runner = HanabiRunner({"all_args": args, "envs": envs, "eval_envs": None, "num_agents": args.num_agents,
+    runner = HanabiRunner({"all_args": args, "envs": envs, "eval_envs": eval_envs, "num_agents": args.num_agents,
                            "device": device, "run_dir": run_dir})
     if stub:
         runner.trainer.policy.get_actions = stub_get_actions
@@ -128,9 +147,66 @@ def recorded(gold, players):
     return fields, {"moves": int(z[key + "moves"]), "games": int(z[key + "games"]), "mean_score": float(z[key + "mean_score"])}
 
 
+def fake_descriptor(struct_cls, **ints):
+    """A ``struct_cls`` of onpolicy._native: every pointer a distinct, never dereferenced, 16-byte aligned address; ``ints`` set."""
+    d = struct_cls()
+    for i, (name, kind) in enumerate(struct_cls._fields_):
+        if kind is ctypes.c_void_p:
+            setattr(d, name, 0x10000 + 0x100 * i)
+    for name, value in ints.items():
+        setattr(d, name, value)
+    return d
+
+
+def header_layout(struct_cls, c_name):
+    """``struct_cls`` against ``typedef struct <c_name> { ... } <c_name>_t;`` of include/mappo_hip.h: the same fields in the
+    same order, pointer for pointer and integer for integer.  -> (the header's text, the number of pointers)."""
+    src = open(HEADER).read()
+    body = src[src.index("typedef struct %s {" % c_name):src.index("} %s_t;" % c_name)]
+    declared = re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(\w+);", body, flags=re.M)
+    assert [name for _, name in declared] == [name for name, _ in struct_cls._fields_]
+    for (ctype, name), (_, kind) in zip(declared, struct_cls._fields_):
+        want = ctypes.c_void_p if "*" in ctype else {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}[ctype.strip()]
+        assert kind is want, name
+    return src, sum(1 for _, kind in struct_cls._fields_ if kind is ctypes.c_void_p)
+
+
+def same_bits(a, b, what):
+    """Two dicts of tensors: the same dtypes, shapes and bits."""
+    for k in a:
+        x, y = a[k], b[k]
+        assert x.dtype == y.dtype and x.shape == y.shape, (what, k)
+        if x.dtype.is_floating_point:
+            x, y = x.contiguous().view(torch.int32), y.contiguous().view(torch.int32)
+        assert torch.equal(x, y), "%s: %s differs" % (what, k)
+
+
 def assert_same(a, b, what):
     (fa, ca), (fb, cb) = a, b
     assert ca == cb, (what, ca, cb)
     for k in sorted(fa):
         assert fa[k].shape == fb[k].shape and fa[k].dtype == fb[k].dtype, (what, k)
         assert np.array_equal(fa[k], fb[k], equal_nan=True), "%s: %s differs" % (what, k)
+
+
+class Arena(object):
+    """Tensors on ``device`` cut out of allocations with ``PAD`` canary elements on either side (NaN for floats, a bit
+    pattern for integers)."""
+    PAD = 64
+
+    def __init__(self, device):
+        self.device, self.whole = device, []
+
+    def put(self, values):
+        values = values.to(self.device)
+        fill = float("nan") if values.dtype.is_floating_point else 0x5a
+        whole = torch.full((values.numel() + 2 * self.PAD,), fill, dtype=values.dtype, device=self.device)
+        inner = whole[self.PAD:self.PAD + values.numel()]
+        inner.copy_(values.reshape(-1))
+        self.whole.append((whole, fill))
+        assert inner.data_ptr() % 16 == 0
+        return inner.view(values.shape)
+
+    def canaries_intact(self):
+        edges = [(edge, fill) for whole, fill in self.whole for edge in (whole[:self.PAD], whole[-self.PAD:])]
+        return all(bool((torch.isnan(e) if e.dtype.is_floating_point else e == fill).all()) for e, fill in edges)

@@ -11,6 +11,8 @@ import torch
 
 from onpolicy.envs.hanabi import batch as hb
 
+import hanabi_turns_common as common
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
@@ -223,38 +225,22 @@ def test_device_equals_host_stepper_under_random_play(rules, share_mode):
     host.close()
 
 
-BUFFER_FIELDS = ("share_obs", "obs", "rnn_states", "rnn_states_critic", "value_preds", "returns", "actions",
-                 "action_log_probs", "rewards", "masks", "bad_masks", "active_masks", "available_actions")
-
-
 def _rollout(tmp_path, tag, on_device, all_obs):
-    from helpers import make_args
     from onpolicy.envs.hanabi.device import HanabiDeviceVecEnv
-    from onpolicy.runner.shared.hanabi_runner_forward import HanabiRunner
-    T, N, A = 8, 7, 2
-    args = make_args(env_name="Hanabi", episode_length=T, n_rollout_threads=N, num_env_steps=2 * T * N, hidden_size=64,
-                     ppo_epoch=2, num_mini_batch=1, algorithm_name="mappo", log_interval=1, use_wandb=False,
-                     use_obs_instead_of_state=all_obs)
-    args.hanabi_name, args.num_agents = "Hanabi-Small", A
-    seeds = [3 + 1000 * i for i in range(N)]
-    envs = HanabiDeviceVecEnv(args, seeds, DEV) if on_device else hb.HanabiBatchVecEnv(args, seeds, copy=False)
-    torch.manual_seed(1)
-    np.random.seed(1)
-    run_dir = tmp_path / tag
-    run_dir.mkdir()
-    runner = HanabiRunner({"all_args": args, "envs": envs, "eval_envs": None, "num_agents": A, "device": DEV,
-                           "run_dir": run_dir})
+    args = common.hanabi_args(2, all_obs=all_obs)
+    envs = HanabiDeviceVecEnv(args, common.SEEDS, DEV) if on_device else hb.HanabiBatchVecEnv(args, common.SEEDS, copy=False)
+    runner = common.make_runner(args, envs, DEV, tmp_path / tag, stub=False)
     scores = []
     collect = runner.collect
 
     def collect_and_keep(step):                             # run() starts a fresh score list every episode
         collect(step)
-        if step == T - 1:
+        if step == common.T - 1:
             scores.append(list(runner.scores))
     runner.collect = collect_and_keep
     runner.run()
     torch.cuda.synchronize()
-    out = {k: _np(getattr(runner.buffer, k)) for k in BUFFER_FIELDS}
+    out = {k: _np(getattr(runner.buffer, k)) for k in common.BUFFER_FIELDS}
     out["params"] = _np(torch.cat([p.detach().reshape(-1) for p in runner.policy.actor.parameters()] +
                                   [p.detach().reshape(-1) for p in runner.policy.critic.parameters()]))
     out["use_rows"] = np.concatenate([_np(t).reshape(-1) for t in (runner.use_obs, runner.use_share_obs,

@@ -19,32 +19,6 @@ import hanabi_turns_common as common
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
-PAD = 64        # canary elements on either side of every allocation
-
-
-class _Arena(object):
-    """Tensors cut out of allocations with canaries around them (NaN for floats, a bit pattern for integers)."""
-
-    def __init__(self):
-        self.whole = []
-
-    def put(self, values):
-        values = values.to(DEV)
-        fill = float("nan") if values.dtype.is_floating_point else 0x5a
-        whole = torch.full((values.numel() + 2 * PAD,), fill, dtype=values.dtype, device=DEV)
-        inner = whole[PAD:PAD + values.numel()]
-        inner.copy_(values.reshape(-1))
-        self.whole.append((whole, fill))
-        assert inner.data_ptr() % 16 == 0
-        return inner.view(values.shape)
-
-    def canaries_intact(self):
-        for whole, fill in self.whole:
-            for edge in (whole[:PAD], whole[-PAD:]):
-                ok = torch.isnan(edge).all() if whole.dtype.is_floating_point else (edge == fill).all()
-                if not bool(ok):
-                    return False
-        return True
 
 
 def _synthetic(n, A, avail_w, rnn_w, recurrent, variant, seed):
@@ -53,7 +27,7 @@ def _synthetic(n, A, avail_w, rnn_w, recurrent, variant, seed):
     can-move bit in its flags word."""
     from onpolicy.runner.shared import hanabi_eval
     g = torch.Generator().manual_seed(seed)
-    arena = _Arena()
+    arena = common.Arena(DEV)
     rnd = lambda *shape: arena.put(torch.randn(*shape, generator=g))        # noqa: E731
     with torch.cuda.device(DEV):
         o = hanabi_eval.EvalOperands(torch.zeros(n, 1, device=DEV), torch.zeros(n, avail_w, device=DEV), A, 1, rnn_w, recurrent)
@@ -81,22 +55,12 @@ def _everything(o, policy, flags):
                 action=policy[0], rnn_new=policy[1], flags=flags)
 
 
-def _same_bits(a, b, what):
-    for k in a:
-        x, y = a[k], b[k]
-        assert x.dtype == y.dtype and x.shape == y.shape, (what, k)
-        if x.dtype.is_floating_point:
-            x, y = x.contiguous().view(torch.int32), y.contiguous().view(torch.int32)
-        assert torch.equal(x, y), "%s: %s differs" % (what, k)
-
-
-CAP_TABLES = _native.TURN_MAX_BLOCKS * 4        # one wave per table, four waves a workgroup
 WIDTHS = (1, 2, 3, 4, 5, 6, 7, 8, 20, 64)
-KERNEL_CASES = [(n, A, rec) for n in (1, 3, 193, CAP_TABLES + 1) for A in (2, 5) for rec in (False, True)]
+KERNEL_CASES = [(n, A, rec) for n in (1, 3, 193, common.CAP_TABLES + 1) for A in (2, 5) for rec in (False, True)]
 
 
 def test_widths_cover_every_offset_from_a_16_byte_boundary():
-    assert CAP_TABLES + 1 == 8193
+    assert common.CAP_TABLES + 1 == 8193
     assert {w % 4 for w in WIDTHS} == {0, 1, 2, 3} and {(5 * w) % 4 for w in WIDTHS} == {0, 1, 2, 3}
 
 
@@ -131,8 +95,8 @@ def test_eval_kernels_equal_their_tensor_op_form(monkeypatch, n, A, recurrent):
                 runs.append((after_begin, _everything(o, policy, flags), before))
             what = "agent %d, widths %d / %d, variant %d" % (agent, avail_w, rnn_w, variant)
             for stage, name in ((0, "eval_begin"), (1, "eval_end")):
-                _same_bits(runs[0][stage], runs[2][stage], "%s, %s: kernel vs tensor ops" % (what, name))
-                _same_bits(runs[0][stage], runs[1][stage], "%s, %s: kernel twice" % (what, name))
+                common.same_bits(runs[0][stage], runs[2][stage], "%s, %s: kernel vs tensor ops" % (what, name))
+                common.same_bits(runs[0][stage], runs[1][stage], "%s, %s: kernel twice" % (what, name))
             # what the specification itself must say (so that equality with it means something)
             before, begun, spec = runs[2][2], runs[2][0], runs[2][1]
             m, st = before["can_move"] != 0, before["flags"] & 0xff

@@ -7,7 +7,6 @@ import json
 import os
 import types
 
-import numpy as np
 import pytest
 import torch
 
@@ -19,7 +18,6 @@ import hanabi_turns_common as common
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
-PAD = 64        # canary elements on either side of every allocation
 
 
 def _widths(game, players):
@@ -32,37 +30,12 @@ def _widths(game, players):
     return obs_len + P, own_len + obs_len + P, moves
 
 
-class _Arena(object):
-    """Tensors cut out of allocations with canaries around them (NaN for floats, a bit pattern for integers)."""
-
-    def __init__(self):
-        self.whole = []
-
-    def put(self, values):
-        values = values.to(DEV)
-        fill = float("nan") if values.dtype.is_floating_point else 0x5a
-        whole = torch.full((values.numel() + 2 * PAD,), fill, dtype=values.dtype, device=DEV)
-        inner = whole[PAD:PAD + values.numel()]
-        inner.copy_(values.reshape(-1))
-        self.whole.append((whole, fill))
-        assert inner.data_ptr() % 16 == 0
-        return inner.view(values.shape)
-
-    def canaries_intact(self):
-        for whole, fill in self.whole:
-            for edge in (whole[:PAD], whole[-PAD:]):
-                ok = torch.isnan(edge).all() if whole.dtype.is_floating_point else (edge == fill).all()
-                if not bool(ok):
-                    return False
-        return True
-
-
 def _synthetic(n, A, widths, variant, seed):
     """-> (operands, policy outputs, env outputs, arena): turn tensors pre-filled with random values; table k has
     (status, can_move) number (k + variant) % 8 of {0, 1, 2, 255} x {0, 1} and score (7 k + variant) % 26."""
     from onpolicy.runner.shared import hanabi_turns
     g = torch.Generator().manual_seed(seed)
-    arena = _Arena()
+    arena = common.Arena(DEV)
     rnd = lambda *shape: arena.put(torch.randn(*shape, generator=g))        # noqa: E731
     turn = types.SimpleNamespace()
     for name, w in zip(hanabi_turns.ROW_FIELDS, widths):
@@ -101,18 +74,8 @@ def _everything(o, policy, env):
     return named
 
 
-def _same_bits(a, b, what):
-    for k in a:
-        x, y = a[k], b[k]
-        assert x.dtype == y.dtype and x.shape == y.shape, (what, k)
-        if x.dtype.is_floating_point:
-            x, y = x.contiguous().view(torch.int32), y.contiguous().view(torch.int32)
-        assert torch.equal(x, y), "%s: %s differs" % (what, k)
-
-
-CAP_TABLES = _native.TURN_MAX_BLOCKS * 4        # one wave per table, four waves a workgroup
 KERNEL_CASES = [(game, A, n) for game, A in (("Hanabi-Small", 2), ("Hanabi-Full", 2), ("Hanabi-Small", 5), ("Hanabi-Full", 5))
-                for n in (1, 63, 64, 65, 193)] + [("Hanabi-Small", 2, CAP_TABLES + 1), ("synthetic", 2, 65)]
+                for n in (1, 63, 64, 65, 193)] + [("Hanabi-Small", 2, common.CAP_TABLES + 1), ("synthetic", 2, 65)]
 
 
 def test_row_widths_cover_every_offset_from_a_16_byte_boundary():
@@ -147,8 +110,8 @@ def test_turn_kernels_equal_their_tensor_op_form(monkeypatch, game, A, n):
                 runs.append((after_begin, _everything(o, policy, env), arena))
             what = "agent %d, variant %d" % (agent, variant)
             for stage, name in ((0, "turn_begin"), (1, "turn_end")):
-                _same_bits(runs[0][stage], runs[2][stage], "%s, %s: kernel vs tensor ops" % (what, name))
-                _same_bits(runs[0][stage], runs[1][stage], "%s, %s: kernel twice" % (what, name))
+                common.same_bits(runs[0][stage], runs[2][stage], "%s, %s: kernel vs tensor ops" % (what, name))
+                common.same_bits(runs[0][stage], runs[1][stage], "%s, %s: kernel twice" % (what, name))
             if n >= 8:      # the ground the case claims to cover
                 spec = runs[2][1]
                 st = spec["flags"] & 0xff

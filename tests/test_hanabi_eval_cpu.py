@@ -3,27 +3,18 @@ tensors against the untouched host ``_eval_games`` on the same stepper, the argu
 (include/mappo_hip.h), the scripts' flag and the move bound."""
 import ctypes
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
-from host_buffer import HostSharedBuffer
 from onpolicy import _native
 
 import hanabi_eval_common as ec
 import hanabi_turns_common as common
+from hanabi_turns_common import host_buffer      # noqa: F401  (a fixture)
 
 CPU = torch.device("cpu")
-
-
-@pytest.fixture
-def host_buffer(monkeypatch):
-    import onpolicy.runner.shared.base_runner as base
-    monkeypatch.setattr(base, "SharedReplayBuffer", HostSharedBuffer)
 
 
 @pytest.mark.parametrize("players", [2, 3])
@@ -64,13 +55,7 @@ def test_feed_forward_policy_carries_no_state(host_buffer, tmp_path):
 
 
 def _fake_descriptor():
-    """Every pointer set to a distinct, never dereferenced, 16-byte aligned address."""
-    d = _native.HanabiEval()
-    for i, (name, kind) in enumerate(_native.HanabiEval._fields_):
-        if kind is ctypes.c_void_p:
-            setattr(d, name, 0x10000 + 0x100 * i)
-    d.n_tables, d.players, d.avail_w, d.rnn_w = 7, 3, 11, 64
-    return d
+    return common.fake_descriptor(_native.HanabiEval, n_tables=7, players=3, avail_w=11, rnn_w=64)
 
 
 def test_eval_entry_points_check_their_arguments_before_enqueueing():
@@ -111,22 +96,11 @@ def test_eval_entry_points_check_their_arguments_before_enqueueing():
 
 
 def test_eval_descriptor_layout_matches_the_header():
-    src = open(os.path.join(ROOT, "include", "mappo_hip.h")).read()
-    body = src[src.index("typedef struct mappo_hanabi_eval {"):src.index("} mappo_hanabi_eval_t;")]
-    declared = re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(\w+);", body, flags=re.M)
-    assert [name for _, name in declared] == [name for name, _ in _native.HanabiEval._fields_]
-    for (ctype, name), (_, kind) in zip(declared, _native.HanabiEval._fields_):
-        want = ctypes.c_void_p if "*" in ctype else {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}[ctype.strip()]
-        assert kind is want, name
-    pointers = sum(1 for _, kind in _native.HanabiEval._fields_ if kind is ctypes.c_void_p)
+    src, pointers = common.header_layout(_native.HanabiEval, "mappo_hanabi_eval")
     assert pointers == 11 and _native.HanabiEval.n_tables.offset == 8 * pointers
     assert _native.HanabiEval.rnn_w.offset == 8 * pointers + 8 + 2 * 4
     assert ctypes.sizeof(_native.HanabiEval) == 8 * pointers + 8 + 4 * 4        # three int32 and the padding to 8 bytes
     assert "K18" in src and "hanabi_runner_forward.py:229" in src
-
-
-ARGV = ["--env_name", "Hanabi", "--hanabi_name", "Hanabi-Small", "--num_agents", "2", "--algorithm_name", "mappo",
-        "--n_rollout_threads", "7", "--episode_length", "8", "--num_env_steps", "112", "--use_wandb"]
 
 
 def test_flag_is_absent_by_default_and_its_refusals_fire(monkeypatch, tmp_path):
@@ -135,23 +109,23 @@ def test_flag_is_absent_by_default_and_its_refusals_fire(monkeypatch, tmp_path):
     from onpolicy.scripts.train import train_hanabi_forward
     monkeypatch.setenv("MAPPO_RESULTS_DIR", str(tmp_path / "results"))
     for script in (train_hanabi_forward, eval_hanabi):
-        plain = script.parse_args(ARGV, get_config())
+        plain = script.parse_args(common.ARGV, get_config())
         assert not hasattr(plain, "use_device_eval")
-        given = script.parse_args(ARGV + ["--use_eval", "--use_device_eval"], get_config())
+        given = script.parse_args(common.ARGV + ["--use_eval", "--use_device_eval"], get_config())
         assert given.use_device_eval is True
         rest = {k: v for k, v in vars(given).items() if k not in ("use_device_eval", "use_eval")}
         assert rest == {k: v for k, v in vars(plain).items() if k != "use_eval"}
     with pytest.raises(NotImplementedError, match="--use_eval"):
-        train_hanabi_forward.main(ARGV + ["--use_device_eval"])
+        train_hanabi_forward.main(common.ARGV + ["--use_device_eval"])
     with pytest.raises(NotImplementedError, match="--use_subproc_envs"):
-        train_hanabi_forward.main(ARGV + ["--use_eval", "--use_device_eval", "--use_subproc_envs"])
+        train_hanabi_forward.main(common.ARGV + ["--use_eval", "--use_device_eval", "--use_subproc_envs"])
     with pytest.raises(NotImplementedError, match="--use_subproc_envs"):
-        eval_hanabi.main(ARGV + ["--use_eval", "--use_device_eval", "--use_subproc_envs", "--model_dir", str(tmp_path)])
-    given = train_hanabi_forward.parse_args(ARGV + ["--use_eval", "--use_device_eval"], get_config())
+        eval_hanabi.main(common.ARGV + ["--use_eval", "--use_device_eval", "--use_subproc_envs", "--model_dir", str(tmp_path)])
+    given = train_hanabi_forward.parse_args(common.ARGV + ["--use_eval", "--use_device_eval"], get_config())
     assert train_hanabi_forward.check_device_eval(given) is True
     with pytest.raises(NotImplementedError, match="GPU device"):
         train_hanabi_forward.check_device_eval(given, CPU)
-    assert train_hanabi_forward.check_device_eval(train_hanabi_forward.parse_args(ARGV, get_config()), CPU) is False
+    assert train_hanabi_forward.check_device_eval(train_hanabi_forward.parse_args(common.ARGV, get_config()), CPU) is False
 
 
 def test_move_bound_follows_from_the_rules_and_stops_an_endless_evaluation(host_buffer, tmp_path, monkeypatch):

@@ -2,27 +2,18 @@
 eager loop on CPU tensors against the default route on the same host stepper, the argument checks and struct layout of
 K17's C ABI (include/mappo_hip.h), and the train script's flag."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
-from host_buffer import HostSharedBuffer
 from onpolicy import _native
 from onpolicy.envs.hanabi import batch as hb
 
 import hanabi_turns_common as common
+from hanabi_turns_common import host_buffer      # noqa: F401  (a fixture)
 
 CPU = torch.device("cpu")
-
-
-@pytest.fixture
-def host_buffer(monkeypatch):
-    import onpolicy.runner.shared.base_runner as base
-    monkeypatch.setattr(base, "SharedReplayBuffer", HostSharedBuffer)
 
 
 @pytest.mark.parametrize("players", [2, 3])
@@ -70,13 +61,7 @@ def test_device_turns_route_equals_default_route_on_host_tables(host_buffer, tmp
 
 
 def _fake_descriptor():
-    """Every pointer set to a distinct, never dereferenced, 16-byte aligned address."""
-    d = _native.HanabiTurn()
-    for i, (name, kind) in enumerate(_native.HanabiTurn._fields_):
-        if kind is ctypes.c_void_p:
-            setattr(d, name, 0x10000 + 0x100 * i)
-    d.n_tables, d.players, d.obs_w, d.share_w, d.avail_w = 7, 3, 13, 21, 11
-    return d
+    return common.fake_descriptor(_native.HanabiTurn, n_tables=7, players=3, obs_w=13, share_w=21, avail_w=11)
 
 
 def test_turn_entry_points_check_their_arguments_before_enqueueing():
@@ -116,36 +101,25 @@ def test_turn_entry_points_check_their_arguments_before_enqueueing():
 
 
 def test_turn_descriptor_layout_matches_the_header():
-    src = open(os.path.join(ROOT, "include", "mappo_hip.h")).read()
-    body = src[src.index("typedef struct mappo_hanabi_turn {"):src.index("} mappo_hanabi_turn_t;")]
-    declared = re.findall(r"^\s*((?:const\s+)?\w+\s*\*?)\s*(\w+);", body, flags=re.M)
-    assert [name for _, name in declared] == [name for name, _ in _native.HanabiTurn._fields_]
-    for (ctype, name), (_, kind) in zip(declared, _native.HanabiTurn._fields_):
-        want = ctypes.c_void_p if "*" in ctype else {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32}[ctype.strip()]
-        assert kind is want, name
-    pointers = sum(1 for _, kind in _native.HanabiTurn._fields_ if kind is ctypes.c_void_p)
+    src, pointers = common.header_layout(_native.HanabiTurn, "mappo_hanabi_turn")
     assert pointers == 25 and _native.HanabiTurn.n_tables.offset == 8 * pointers
     assert ctypes.sizeof(_native.HanabiTurn) == 8 * pointers + 8 + 4 * 4
     assert "#define MAPPO_TURN_MAX_BLOCKS %d\n" % _native.TURN_MAX_BLOCKS in src
     assert "#define MAPPO_TURN_MAX_PLAYERS %d\n" % _native.TURN_MAX_PLAYERS in src
 
 
-ARGV = ["--env_name", "Hanabi", "--hanabi_name", "Hanabi-Small", "--num_agents", "2", "--algorithm_name", "mappo",
-        "--n_rollout_threads", "7", "--episode_length", "8", "--num_env_steps", "112", "--use_wandb"]
-
-
 def test_flag_is_absent_by_default_and_needs_device_tables(monkeypatch, tmp_path):
     from onpolicy.config import get_config
     from onpolicy.scripts.train import train_hanabi_forward
     monkeypatch.setenv("MAPPO_RESULTS_DIR", str(tmp_path / "results"))
-    plain = train_hanabi_forward.parse_args(ARGV, get_config())
+    plain = train_hanabi_forward.parse_args(common.ARGV, get_config())
     assert not hasattr(plain, "use_device_turns") and not hasattr(plain, "use_device_env")
-    given = train_hanabi_forward.parse_args(ARGV + ["--use_device_env", "--use_device_turns"], get_config())
+    given = train_hanabi_forward.parse_args(common.ARGV + ["--use_device_env", "--use_device_turns"], get_config())
     assert given.use_device_turns is True and given.use_device_env is True
     rest = {k: v for k, v in vars(given).items() if k not in ("use_device_turns", "use_device_env")}
     assert rest == vars(plain)
     with pytest.raises(NotImplementedError, match="--use_device_env"):
-        train_hanabi_forward.main(ARGV + ["--use_device_turns"])
+        train_hanabi_forward.main(common.ARGV + ["--use_device_turns"])
 
 
 def test_recurrent_policy_stays_on_the_default_device_route(host_buffer, tmp_path, capsys):
