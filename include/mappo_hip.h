@@ -981,6 +981,64 @@ typedef struct mappo_hanabi_turn {
 int mappo_hanabi_turn_begin(const mappo_hanabi_turn_t* args, int agent, mappo_stream_t stream);
 int mappo_hanabi_turn_end(const mappo_hanabi_turn_t* args, int agent, mappo_stream_t stream);
 
+/* K17 for a recurrent policy: the same two launches, which also keep the two RNN state tensors of the turn (what
+ * HanabiRunner.collect does with turn_rnn_states / turn_rnn_states_critic around the env step, same reference lines).  The
+ * descriptor is K17's, field for field, followed by
+ *   rnn_states, rnn_states_critic, contiguous [n_tables, players, rnn_w] float32 (rnn_w = recurrent_N * hidden_size): the
+ *     actor's and the critic's state per (table, player);
+ *   rnn_new, rnn_new_critic [n_tables, rnn_w]: the policy's new states on ALL rows.
+ * These four must be 16-byte aligned; a slot row sits at (n * players + agent) * rnn_w floats, rnn_w need not be a multiple
+ * of four.  K17's requirements hold for the other operands.
+ *
+ * mappo_hanabi_turn_begin_rnn(agent), per table n with m = can_move[n] != 0: everything mappo_hanabi_turn_begin does, then
+ *   if m: rnn_states[n, agent, :] = rnn_new[n, :]; rnn_states_critic[n, agent, :] = rnn_new_critic[n, :].
+ *   A table that sits out keeps both states: what the policy computed for it is discarded.
+ * mappo_hanabi_turn_end_rnn(agent), per table n: everything mappo_hanabi_turn_end does, in its order, then
+ *   if status == 1:  rnn_states[n, a, :] = rnn_states_critic[n, a, :] = 0 for EVERY player a (not only a > agent).
+ * One launch each, K17's kernels instantiated on this descriptor.  MAPPO_E_NULL (a pointer the call reads or writes: all
+ * four state pointers in _begin_rnn; in _end_rnn the two state tensors -- rnn_new / rnn_new_critic may be NULL there),
+ * MAPPO_E_SHAPE (K17's cases; rnn_w <= 0 or rnn_w > INT32_MAX / 5) and MAPPO_E_ALIGN (K17's cases; one of the four state
+ * arrays not 16-byte aligned) are returned before anything is enqueued. */
+typedef struct mappo_hanabi_turn_rnn {
+    float* obs;
+    float* share_obs;
+    float* available_actions;
+    float* values;
+    float* actions;
+    float* action_log_probs;
+    float* rewards;
+    float* rewards_since_last_action;
+    float* masks;
+    float* active_masks;
+    float* use_obs;
+    float* use_share_obs;
+    float* use_available_actions;
+    const float* value;
+    const int64_t* action;
+    const float* logp;
+    const int32_t* flags;
+    const float* rewards_env;
+    int32_t* can_move;
+    uint8_t* reset_choose;
+    int32_t* env_actions;
+    int64_t* moves;
+    int32_t* games;
+    int32_t* score_sum;
+    uint8_t* refused;
+    float* rnn_states;
+    float* rnn_states_critic;
+    const float* rnn_new;
+    const float* rnn_new_critic;
+    int64_t n_tables;
+    int32_t players;
+    int32_t obs_w;
+    int32_t share_w;
+    int32_t avail_w;
+    int32_t rnn_w;
+} mappo_hanabi_turn_rnn_t;
+int mappo_hanabi_turn_begin_rnn(const mappo_hanabi_turn_rnn_t* args, int agent, mappo_stream_t stream);
+int mappo_hanabi_turn_end_rnn(const mappo_hanabi_turn_rnn_t* args, int agent, mappo_stream_t stream);
+
 /* ------------------------------------------------- K18: the bookkeeping of a Hanabi EVALUATION move, from the flags words ----
  * What HanabiRunner.eval does around the env step of one player's move (reference
  * onpolicy/runner/shared/hanabi_runner_forward.py:229 onwards: the choose mask, the -1 actions of the tables that sit out,

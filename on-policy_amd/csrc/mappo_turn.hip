@@ -11,6 +11,10 @@
 // read as float4 too when the source row sits at the same offset from a 16-byte boundary as the destination row (else as
 // four dwords: still consecutive lanes on consecutive addresses).  No LDS, no atomics, nothing allocated.
 //
+// K17 for a recurrent policy (mappo_hanabi_turn_begin_rnn / _end_rnn): the same two kernels, instantiated on a descriptor that
+// also carries the actor's and the critic's RNN state per (table, player) -- the movers' new states go into slot `agent`, a
+// finished table's states are cleared for every player.
+//
 // K18: the same two launches for an EVALUATION move (include/mappo_hip.h, "K18"): no buffer slots, rewards or masks, but the
 // actor's RNN state per (table, player), a final score per table, and finished tables that never restart.  Same shape, same
 // row helpers.
@@ -61,7 +65,14 @@ __device__ __forceinline__ void zero_row(float* dst, size_t d0, int w, int lane)
     }
 }
 
-__global__ void __launch_bounds__(kThreads) hanabi_turn_begin_kernel(mappo_hanabi_turn_t d, int agent) {
+// The training move's two kernels stand once, for both descriptors: D = mappo_hanabi_turn_t (K17) or mappo_hanabi_turn_rnn_t
+// (the same fields in front, then the carried RNN states of a recurrent policy).  What kRnn guards is compiled into the
+// second instantiation only.
+template <typename D> constexpr bool kRnn = false;
+template <> constexpr bool kRnn<mappo_hanabi_turn_rnn_t> = true;
+
+template <typename D>
+__global__ void __launch_bounds__(kThreads) hanabi_turn_begin_kernel(D d, int agent) {
     const int lane = threadIdx.x & 63;
     const long long first = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6), step = (long long)gridDim.x * kWaves;
     const size_t A = (size_t)d.players;
@@ -78,10 +89,15 @@ __global__ void __launch_bounds__(kThreads) hanabi_turn_begin_kernel(mappo_hanab
         copy_row(d.obs, slot * d.obs_w, d.use_obs, (size_t)n * d.obs_w, d.obs_w, lane);
         copy_row(d.share_obs, slot * d.share_w, d.use_share_obs, (size_t)n * d.share_w, d.share_w, lane);
         copy_row(d.available_actions, slot * d.avail_w, d.use_available_actions, (size_t)n * d.avail_w, d.avail_w, lane);
+        if constexpr (kRnn<D>) {
+            copy_row(d.rnn_states, slot * d.rnn_w, d.rnn_new, (size_t)n * d.rnn_w, d.rnn_w, lane);
+            copy_row(d.rnn_states_critic, slot * d.rnn_w, d.rnn_new_critic, (size_t)n * d.rnn_w, d.rnn_w, lane);
+        }
     }
 }
 
-__global__ void __launch_bounds__(kThreads) hanabi_turn_end_kernel(mappo_hanabi_turn_t d, int agent) {
+template <typename D>
+__global__ void __launch_bounds__(kThreads) hanabi_turn_end_kernel(D d, int agent) {
     const int lane = threadIdx.x & 63;
     const long long first = (long long)blockIdx.x * kWaves + (threadIdx.x >> 6), step = (long long)gridDim.x * kWaves;
     const int A = d.players;
@@ -123,6 +139,11 @@ __global__ void __launch_bounds__(kThreads) hanabi_turn_end_kernel(mappo_hanabi_
             zero_row(d.obs, (row + a) * d.obs_w, d.obs_w, lane);
             zero_row(d.share_obs, (row + a) * d.share_w, d.share_w, lane);
         }
+        if constexpr (kRnn<D>) {
+            // every player's state restarts with the game: the A slot rows of a table are one stretch of A * rnn_w floats
+            zero_row(d.rnn_states, row * d.rnn_w, A * d.rnn_w, lane);
+            zero_row(d.rnn_states_critic, row * d.rnn_w, A * d.rnn_w, lane);
+        }
     }
 }
 
@@ -162,17 +183,29 @@ __global__ void __launch_bounds__(kThreads) hanabi_eval_end_kernel(mappo_hanabi_
     }
 }
 
+unsigned grid_of(long long n) {
+    const long long blocks = (n + kWaves - 1) / kWaves;
+    return (unsigned)(blocks < MAPPO_TURN_MAX_BLOCKS ? blocks : MAPPO_TURN_MAX_BLOCKS);
+}
+
 // `used`: the pointers this entry point reads or writes (the other one's may be NULL).
-template <size_t K>
-int check(const mappo_hanabi_turn_t* d, int agent, const void* const (&used)[K]) {
+template <typename D, size_t K>
+int check(const D* d, int agent, const void* const (&used)[K]) {
     for (const void* p : used)
         if (!p) return MAPPO_E_NULL;
     if (d->n_tables <= 0 || d->players < 1 || d->players > MAPPO_TURN_MAX_PLAYERS || agent < 0 || agent >= d->players ||
         d->obs_w <= 0 || d->share_w <= 0 || d->avail_w <= 0)
         return MAPPO_E_SHAPE;
+    if constexpr (kRnn<D>)
+        if (d->rnn_w <= 0 || d->rnn_w > INT32_MAX / MAPPO_TURN_MAX_PLAYERS) return MAPPO_E_SHAPE;    // (players * rnn_w: an int)
     const void* rows[] = {d->obs, d->share_obs, d->available_actions, d->use_obs, d->use_share_obs, d->use_available_actions};
     for (const void* p : rows)
         if (!mappo::aligned_to(p, 16)) return MAPPO_E_ALIGN;
+    if constexpr (kRnn<D>) {
+        const void* states[] = {d->rnn_states, d->rnn_states_critic, d->rnn_new, d->rnn_new_critic};
+        for (const void* p : states)
+            if (!mappo::aligned_to(p, 16)) return MAPPO_E_ALIGN;
+    }
     if (!mappo::aligned_to(d->moves, 8) || !mappo::aligned_to(d->action, 8)) return MAPPO_E_ALIGN;
     const void* words[] = {d->values, d->actions, d->action_log_probs, d->rewards, d->rewards_since_last_action, d->masks,
                            d->active_masks, d->value, d->logp, d->flags, d->rewards_env, d->can_move, d->env_actions,
@@ -180,6 +213,14 @@ int check(const mappo_hanabi_turn_t* d, int agent, const void* const (&used)[K])
     for (const void* p : words)
         if (!mappo::aligned_to(p, 4)) return MAPPO_E_ALIGN;
     return 0;
+}
+
+template <typename D, size_t K>
+int enqueue(void (*kernel)(D, int), const D* d, int agent, const void* const (&used)[K], mappo_stream_t stream_) {
+    const int rc = check(d, agent, used);
+    if (rc != 0) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid_of(d->n_tables)), dim3(kThreads), 0, static_cast<hipStream_t>(stream_), *d, agent);
+    return (int)hipGetLastError();
 }
 
 template <size_t K>
@@ -200,37 +241,41 @@ int check_eval(const mappo_hanabi_eval_t* d, int agent, const void* const (&used
     return 0;
 }
 
-unsigned grid_of(long long n) {
-    const long long blocks = (n + kWaves - 1) / kWaves;
-    return (unsigned)(blocks < MAPPO_TURN_MAX_BLOCKS ? blocks : MAPPO_TURN_MAX_BLOCKS);
-}
-
 }  // namespace
+
+// the pointers the begin / end operation reads or writes, whichever descriptor carries them
+#define TURN_BEGIN_USES(d) d.obs, d.share_obs, d.available_actions, d.values, d.actions, d.action_log_probs, d.use_obs, \
+                           d.use_share_obs, d.use_available_actions, d.value, d.action, d.logp, d.can_move, d.env_actions
+#define TURN_END_USES(d) d.obs, d.share_obs, d.values, d.rewards, d.rewards_since_last_action, d.masks, d.active_masks, \
+                         d.use_available_actions, d.flags, d.rewards_env, d.can_move, d.reset_choose, d.moves, d.games, \
+                         d.score_sum, d.refused
 
 extern "C" int mappo_hanabi_turn_begin(const mappo_hanabi_turn_t* args, int agent, mappo_stream_t stream_) {
     if (!args) return MAPPO_E_NULL;
     const mappo_hanabi_turn_t& d = *args;
-    const void* const used[] = {d.obs, d.share_obs, d.available_actions, d.values, d.actions, d.action_log_probs, d.use_obs,
-                                d.use_share_obs, d.use_available_actions, d.value, d.action, d.logp, d.can_move,
-                                d.env_actions};
-    const int rc = check(args, agent, used);
-    if (rc != 0) return rc;
-    hipLaunchKernelGGL(hanabi_turn_begin_kernel, dim3(grid_of(args->n_tables)), dim3(kThreads), 0,
-                       static_cast<hipStream_t>(stream_), *args, agent);
-    return (int)hipGetLastError();
+    const void* const used[] = {TURN_BEGIN_USES(d)};
+    return enqueue(hanabi_turn_begin_kernel<mappo_hanabi_turn_t>, args, agent, used, stream_);
 }
 
 extern "C" int mappo_hanabi_turn_end(const mappo_hanabi_turn_t* args, int agent, mappo_stream_t stream_) {
     if (!args) return MAPPO_E_NULL;
     const mappo_hanabi_turn_t& d = *args;
-    const void* const used[] = {d.obs, d.share_obs, d.values, d.rewards, d.rewards_since_last_action, d.masks, d.active_masks,
-                                d.use_available_actions, d.flags, d.rewards_env, d.can_move, d.reset_choose, d.moves,
-                                d.games, d.score_sum, d.refused};
-    const int rc = check(args, agent, used);
-    if (rc != 0) return rc;
-    hipLaunchKernelGGL(hanabi_turn_end_kernel, dim3(grid_of(args->n_tables)), dim3(kThreads), 0,
-                       static_cast<hipStream_t>(stream_), *args, agent);
-    return (int)hipGetLastError();
+    const void* const used[] = {TURN_END_USES(d)};
+    return enqueue(hanabi_turn_end_kernel<mappo_hanabi_turn_t>, args, agent, used, stream_);
+}
+
+extern "C" int mappo_hanabi_turn_begin_rnn(const mappo_hanabi_turn_rnn_t* args, int agent, mappo_stream_t stream_) {
+    if (!args) return MAPPO_E_NULL;
+    const mappo_hanabi_turn_rnn_t& d = *args;
+    const void* const used[] = {TURN_BEGIN_USES(d), d.rnn_states, d.rnn_states_critic, d.rnn_new, d.rnn_new_critic};
+    return enqueue(hanabi_turn_begin_kernel<mappo_hanabi_turn_rnn_t>, args, agent, used, stream_);
+}
+
+extern "C" int mappo_hanabi_turn_end_rnn(const mappo_hanabi_turn_rnn_t* args, int agent, mappo_stream_t stream_) {
+    if (!args) return MAPPO_E_NULL;
+    const mappo_hanabi_turn_rnn_t& d = *args;
+    const void* const used[] = {TURN_END_USES(d), d.rnn_states, d.rnn_states_critic};
+    return enqueue(hanabi_turn_end_kernel<mappo_hanabi_turn_rnn_t>, args, agent, used, stream_);
 }
 
 extern "C" int mappo_hanabi_eval_begin(const mappo_hanabi_eval_t* args, int agent, mappo_stream_t stream_) {

@@ -130,6 +130,13 @@ class HanabiTurn(ctypes.Structure):
                [("n_tables", _i64)] + [(n, ctypes.c_int32) for n in ("players", "obs_w", "share_w", "avail_w")]
 
 
+class HanabiTurnRnn(ctypes.Structure):
+    """struct mappo_hanabi_turn_rnn (include/mappo_hip.h): K17's operands, then the RNN states of a recurrent policy."""
+    _fields_ = [f for f in HanabiTurn._fields_ if f[1] is _vp] + \
+               [(n, _vp) for n in ("rnn_states", "rnn_states_critic", "rnn_new", "rnn_new_critic")] + \
+               [("n_tables", _i64)] + [(n, ctypes.c_int32) for n in ("players", "obs_w", "share_w", "avail_w", "rnn_w")]
+
+
 class HanabiEval(ctypes.Structure):
     """struct mappo_hanabi_eval (include/mappo_hip.h): every operand of K18's two launches."""
     _fields_ = [(n, _vp) for n in ("use_available_actions", "rnn_states", "rnn_new", "action", "flags", "can_move",
@@ -232,6 +239,8 @@ SIGNATURES = {
     # K17
     "mappo_hanabi_turn_begin": (_int, [ctypes.POINTER(HanabiTurn), _int, _vp]),
     "mappo_hanabi_turn_end": (_int, [ctypes.POINTER(HanabiTurn), _int, _vp]),
+    "mappo_hanabi_turn_begin_rnn": (_int, [ctypes.POINTER(HanabiTurnRnn), _int, _vp]),
+    "mappo_hanabi_turn_end_rnn": (_int, [ctypes.POINTER(HanabiTurnRnn), _int, _vp]),
     # K18
     "mappo_hanabi_eval_begin": (_int, [ctypes.POINTER(HanabiEval), _int, _vp]),
     "mappo_hanabi_eval_end": (_int, [ctypes.POINTER(HanabiEval), _int, _vp]),

@@ -48,6 +48,11 @@ class _HostStage(object):
         return out
 
 
+def recurrent_policy(all_args):
+    """Whether the run's policy carries RNN states (either recurrent flag)."""
+    return bool(getattr(all_args, "use_recurrent_policy", False) or getattr(all_args, "use_naive_recurrent_policy", False))
+
+
 class _Route(object):
     def __init__(self, runner):
         self.r = runner
@@ -195,7 +200,9 @@ class DeviceTurns(_Route):
     marks are a device mask that ``restart()`` consumes and clears, the counters per-table accumulators.  NOT the
     host-decided routes' trajectories: the sampler's noise tensor is [N, moves] instead of [movers, moves], so from the
     first move with a table sitting out the same generator state gives other draws (hence opt-in); with a policy whose
-    outputs do not depend on the batch the routes agree bit for bit (tests/test_hanabi_turns_cpu.py)."""
+    outputs do not depend on the batch the routes agree bit for bit (tests/test_hanabi_turns_cpu.py).  A recurrent policy
+    (``--use_device_turns_rnn``) has its two RNN states per (table, player) kept by the same two launches: recurrent
+    operands, whose state tensors a captured move snapshots with the rest (tests/test_hanabi_turns_rnn_cpu.py)."""
     name = "device_turns"
 
     def warmup(self):
@@ -203,7 +210,8 @@ class DeviceTurns(_Route):
         r, e = self.r, self.r.envs
         self.use_obs, self.use_available_actions = e.step_obs, e.step_available_actions
         self.use_share_obs = e.step_share_obs if r.use_centralized_V else e.step_obs
-        self.ops = hanabi_turns.TurnOperands(r.turn, self.use_obs, self.use_share_obs, self.use_available_actions)
+        self.ops = hanabi_turns.TurnOperands(r.turn, self.use_obs, self.use_share_obs, self.use_available_actions,
+                                             recurrent=recurrent_policy(r.all_args))
         self.ops.reset_choose.fill_(1)
         self.restart()
         self.turn_graphs = hanabi_moves.build(r, self, e, r.n_rollout_threads, r.buffer.device, with_value_head=True,
@@ -229,12 +237,13 @@ class DeviceTurns(_Route):
             self.move(agent_id)
 
     def move(self, agent_id):
-        """Forward on all N rows, ``turn_begin``, the env step, ``turn_end``: launches only (what the graphs capture)."""
+        """Forward on all N rows, ``turn_begin``, the env step, ``turn_end``: launches only (what the graphs capture).  A
+        recurrent policy's new states go where its outputs go: the movers' into slot ``agent_id`` (recurrent operands)."""
         r, turn, o, e = self.r, self.r.turn, self.ops, self.r.envs
-        value, action, action_log_prob, _, _ = r.trainer.policy.get_actions(
+        value, action, action_log_prob, rnn_state, rnn_state_critic = r.trainer.policy.get_actions(
             self.use_share_obs, self.use_obs, turn.rnn_states[:, agent_id], turn.rnn_states_critic[:, agent_id],
             turn.masks[:, agent_id], self.use_available_actions)
-        hanabi_turns.turn_begin(o, agent_id, value, action, action_log_prob)
+        hanabi_turns.turn_begin(o, agent_id, value, action, action_log_prob, rnn_state, rnn_state_critic)
         e.step_device(o.env_actions)
         hanabi_turns.turn_end(o, agent_id, e.step_flags, e.step_rewards)
 

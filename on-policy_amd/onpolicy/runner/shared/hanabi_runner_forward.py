@@ -58,10 +58,11 @@ class HanabiRunner(Runner):
             self.device_eval = hanabi_eval.DeviceEval(self)
 
     def _device_turns_refusal(self):
-        """Why this runner cannot take the host-free route (None: it can)."""
+        """Why this runner cannot take the host-free route (None: it can).  A recurrent policy takes it with a second opt-in
+        (``--use_device_turns_rnn``: the moves then keep its two RNN states, hanabi_turns.py)."""
         from onpolicy.algorithms.utils import distributions
         args, space = self.all_args, self.envs.action_space[0]
-        if getattr(args, "use_recurrent_policy", False) or getattr(args, "use_naive_recurrent_policy", False):
+        if hanabi_routes.recurrent_policy(args) and not getattr(args, "use_device_turns_rnn", False):
             return "a recurrent policy carries per-table state through the moves"
         if distributions.SAMPLING_RNG != "device":
             return "--sampler_rng host draws on the CPU generator"

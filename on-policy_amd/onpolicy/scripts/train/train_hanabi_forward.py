@@ -15,7 +15,9 @@ games restart are read off the tables' flags words on the device (K17), the poli
 replayed from a captured graph -- a buffer step copies nothing to the host.  Same game, same policy, but NOT the default
 route's trajectories: the sampler's noise tensor is [N, moves] instead of [movers, moves], so the same generator state gives
 different draws as soon as one table sits a move out (another sample of the same distribution; see
-runner/shared/hanabi_runner_forward.py).
+runner/shared/hanabi_runner_forward.py).  A recurrent policy (``--use_recurrent_policy``, ``--use_naive_recurrent_policy``)
+stays on the default device route under ``--use_device_turns`` alone; ``--use_device_turns_rnn`` (with it; opt-in) puts it on
+the host-free route as well: the two launches of K17 then also keep the actor's and the critic's RNN state per (table, player).
 
     python -m onpolicy.scripts.train.train_hanabi_forward --env_name Hanabi --hanabi_name Hanabi-Full --num_agents 2 ...
 """
@@ -70,6 +72,9 @@ def parse_args(args, parser):
     parser.add_argument('--use_device_turns', action='store_true', default=argparse.SUPPRESS,
                         help="with --use_device_env: turn bookkeeping on the GPU too (no device -> host copy per move, "
                              "moves replayed from captured graphs); samples other trajectories than the default route")
+    parser.add_argument('--use_device_turns_rnn', action='store_true', default=argparse.SUPPRESS,
+                        help="with --use_device_turns: a recurrent policy takes the host-free route too (its RNN states are "
+                             "kept by the turn kernels); changes nothing for a feed-forward policy")
     parser.add_argument('--use_device_eval', action='store_true', default=argparse.SUPPRESS,
                         help="with --use_eval: keep the EVAL tables on the GPU and play the evaluation without the host "
                              "(K18, captured moves); independent of --use_device_env")
@@ -94,6 +99,8 @@ def main(args):
     all_args.use_device_env = bool(getattr(all_args, "use_device_env", False))
     if getattr(all_args, "use_device_turns", False) and not all_args.use_device_env:
         raise NotImplementedError("--use_device_turns needs --use_device_env (it drives the tables in device memory)")
+    if getattr(all_args, "use_device_turns_rnn", False) and not getattr(all_args, "use_device_turns", False):
+        raise NotImplementedError("--use_device_turns_rnn needs --use_device_turns (it lets a recurrent policy take that route)")
     check_device_eval(all_args)
     device = _launch.device_of(all_args)
     device_eval = check_device_eval(all_args, device)

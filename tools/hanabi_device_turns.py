@@ -6,6 +6,7 @@ captured graph (--use_device_turns).  Protocol and shapes of tools/hanabi_rollou
 steps, ``sh`` (Hanabi-Full, 2 players, 1,000 tables) and ``config5`` (5 players, 8,192 tables), hidden 512 x 2.
 
     python tools/hanabi_device_turns.py [--shapes sh,config5] [--reps 10] [--warmup 1] [--kernel_trace DIR] [--out file.json]
+                                        [--recurrent]
     rocprofv3 --kernel-trace -f csv -o trace -d DIR/config5/default -- python tools/hanabi_device_turns.py --kernels_only default --shapes config5
     rocprofv3 --kernel-trace -f csv -o trace -d DIR/config5/captured -- python tools/hanabi_device_turns.py --kernels_only captured --shapes config5
 
@@ -20,6 +21,9 @@ trace) and nothing else: the run to put under the profiler, on its own.  ``--ker
 such runs left under DIR/<shape>/<way> and adds the launches per player move of both routes (every launch of a buffer
 step -- chooseinsert, reset and merge included -- over steps x players) and, for ``turn_begin`` (the memory-bound launch
 of K17), its bytes -- 2 x tables x row bytes -- over its average time as a share of the HBM peak (8.0 TB/s).
+``--recurrent``: the same three ways with the recurrent policy of the reference's eval script (rmappo, hidden 512 x 2,
+recurrent_N 1); the host-free ways then also take ``--use_device_turns_rnn`` and K17's two launches keep the actor's and the
+critic's RNN state (profiles/hanabi_device_turns_rnn.json).  ``turn_begin`` then moves 2 x rnn_w more floats per table.
 Prints one JSON line.
 """
 import argparse
@@ -40,7 +44,7 @@ KERNEL_STEPS = 4
 MARKER = "hanabi_draws_kernel"
 
 
-def build_runner(shape, way, steps):
+def build_runner(shape, way, steps, recurrent=False):
     import pathlib
     import numpy as np
     import torch
@@ -48,10 +52,10 @@ def build_runner(shape, way, steps):
     from onpolicy.runner.shared.hanabi_runner_forward import HanabiRunner
     from onpolicy.scripts.train import _launch, train_hanabi_forward
     argv = ["--env_name", "Hanabi", "--hanabi_name", "Hanabi-Full", "--num_agents", str(shape["players"]),
-            "--algorithm_name", "mappo", "--experiment_name", "rollout", "--seed", "1", "--n_training_threads", "1",
-            "--n_rollout_threads", str(shape["tables"]), "--episode_length", str(steps), "--num_env_steps", "1",
+            "--algorithm_name", "rmappo" if recurrent else "mappo", "--experiment_name", "rollout", "--seed", "1",
+            "--n_training_threads", "1", "--n_rollout_threads", str(shape["tables"]), "--episode_length", str(steps), "--num_env_steps", "1",
             "--hidden_size", "512", "--layer_N", "2", "--use_ReLU", "--use_wandb", "--use_device_env"] + \
-        ([] if way == "default" else ["--use_device_turns"])
+        ([] if way == "default" else ["--use_device_turns"] + (["--use_device_turns_rnn"] if recurrent else []))
     all_args = _launch.apply_algorithm_flags(train_hanabi_forward.parse_args(argv, get_config()), ("rmappo", "mappo", "ippo"))
     device = torch.device("cuda", 0)
     torch.manual_seed(1)
@@ -62,6 +66,7 @@ def build_runner(shape, way, steps):
     os.environ["MAPPO_TURN_GRAPH"] = "1" if way == "captured" else "0"      # read when begin_rollout builds the graphs
     runner.begin_rollout()
     assert (runner.route.name == "device_turns") == (way != "default") and (runner.turn_graphs is not None) == (way == "captured")
+    assert bool(runner.policy.actor._recurrent) == recurrent and (way == "default" or runner.route.ops.recurrent == recurrent)
     return runner
 
 
@@ -99,6 +104,7 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--steps", type=int, default=base.STEPS)
     ap.add_argument("--kernels_only", default=None, choices=WAYS)
+    ap.add_argument("--recurrent", action="store_true", help="the recurrent policy (rmappo); host-free ways with --use_device_turns_rnn")
     ap.add_argument("--kernel_trace", default=None)
     ap.add_argument("--commit", default=None)
     ap.add_argument("--out", default=None)
@@ -108,7 +114,7 @@ if __name__ == "__main__":
     assert torch.cuda.is_available(), "a timing needs the GPU"
     out = {"what": "wall time of the collect phase (%d buffer steps, no update) with the tables on the device: default "
                    "device route, device turns eager, device turns captured, alternating, %d repetitions after %d warm-up "
-                   "each" % (opt.steps, opt.reps, opt.warmup),
+                   "each%s" % (opt.steps, opt.reps, opt.warmup, "; recurrent policy (--use_device_turns_rnn)" if opt.recurrent else ""),
            "commit": opt.commit, "hbm_peak_TB_per_s": base.HBM_PEAK_BYTES_PER_S / 1e12, "shapes": {}}
 
     def write():
@@ -120,14 +126,14 @@ if __name__ == "__main__":
     for name in opt.shapes.split(","):
         shape = base.SHAPES[name]
         if opt.kernels_only:
-            runner = build_runner(shape, opt.kernels_only, KERNEL_STEPS)
+            runner = build_runner(shape, opt.kernels_only, KERNEL_STEPS, opt.recurrent)
             collect_phase(runner, KERNEL_STEPS)             # past first-call effects
             runner.envs.batch.draws()                       # marker
             collect_phase(runner, KERNEL_STEPS)
             runner.envs.batch.draws()                       # marker
             torch.cuda.synchronize()
             continue
-        runners = {way: build_runner(shape, way, opt.steps) for way in WAYS}
+        runners = {way: build_runner(shape, way, opt.steps, opt.recurrent) for way in WAYS}
 
         def timed(way):
             torch.cuda.synchronize()
@@ -150,8 +156,11 @@ if __name__ == "__main__":
         s = {way: base.summary(times[way]) for way in WAYS}
         spread = max(s[way]["p90_s"] - s[way]["p10_s"] for way in WAYS)
         env = runners["default"].envs
+        # what turn_begin moves per table: the three rows and, for a recurrent policy, the two new states
+        state_bytes = 2 * 4 * runners["default"].turn.rnn_states[0, 0].numel() if opt.recurrent else 0
+        policy = "rmappo (recurrent, recurrent_N 1)" if opt.recurrent else "mappo"
         gain = s["default"]["median_s"] - s["captured"]["median_s"]
-        rec = {"config": "Hanabi-Full, %d players, %d tables, hidden 512 x 2, mappo, 1 x MI355X" % (shape["players"], shape["tables"]),
+        rec = {"config": "Hanabi-Full, %d players, %d tables, hidden 512 x 2, %s, 1 x MI355X" % (shape["players"], shape["tables"], policy),
                "default_device_route": s["default"], "device_turns_eager": s["eager"], "device_turns_captured": s["captured"],
                "spread_s": round(spread, 4), "spread_is": "the widest of the three ways' 10th-to-90th-percentile widths",
                "captured_faster_than_default_by_s": round(gain, 4),
@@ -161,7 +170,9 @@ if __name__ == "__main__":
                "ms_per_buffer_step": {way: round(1e3 * s[way]["median_s"] / opt.steps, 3) for way in WAYS},
                "ms_per_player_move": {way: round(1e3 * s[way]["median_s"] / opt.steps / shape["players"], 3) for way in WAYS},
                "row_bytes_per_table": base.row_bytes(env),
-               "turn_begin_bytes_per_launch": 2 * base.row_bytes(env) * shape["tables"]}
+               "turn_begin_bytes_per_launch": 2 * (base.row_bytes(env) + state_bytes) * shape["tables"]}
+        if opt.recurrent:
+            rec["state_bytes_per_table"] = state_bytes
         if opt.kernel_trace:
             rec["kernel_trace_note"] = "kernel-trace runs of their own at this shape, %d buffer steps between two markers" % KERNEL_STEPS
             for way, key in (("default", "default_device_route"), ("captured", "device_turns_captured")):
