@@ -254,9 +254,11 @@ int mappo_gather_records(const float* records, int record_width, const mappo_rec
                          int n_fields, const int64_t* idx, int64_t mb, int L, int T, int64_t N, int A,
                          const float* stats, mappo_stream_t stream);
 
-/* Tuning hook for benchmarks (results do not depend on it): bits 0-1 log2 of the loads in
- * flight per lane, bit 2 non-temporal accesses, bits 4.. workgroups per CU (0 = occupancy).
- * Returns the previous value. */
+/* Tuning hook for benchmarks (results do not depend on it): bits 4.. are the workgroups per CU of the
+ * gathers' persistent grid (0 = what occupancy allows).  The low four bits once selected the loads in
+ * flight per lane and non-temporal access; the one shape that is built has two loads in flight and
+ * non-temporal accesses, and those bits are accepted and ignored.  The default is 5.  Returns the
+ * previous value.  Not thread-safe, like the other hooks. */
 int mappo_gather_set_variant(int variant);
 
 /* ------------------------------------------------------------ K2: slab writes ----
@@ -278,11 +280,12 @@ int mappo_slab_copy(const mappo_slab_t* slabs, int n_slabs, mappo_stream_t strea
  * through a resident copy whose rows hold (x - mean) / sqrt(var + eps) (mappo_standardize_rows_ld; the LayerNorm's affine half
  * is folded into the first Linear); when insert / chooseinsert / after_update (shared_buffer.py:90-177) rewrite a slab of the
  * field, the same slab of the copy is recomputed from the VALUE being written -- by extra workgroups of this launch, in the
- * arithmetic of mappo_standardize_rows_ld (bit-identical rows).  src [rows, D] floats; dst [rows, ld >= D] floats, columns
+ * layout mappo_standardize_rows_ld writes (its arithmetic is this function's own, see below: the rows agree with
+ * mappo_standardize_rows_ld to rounding, not bit for bit).  src [rows, D] floats; dst [rows, ld >= D] floats, columns
  * D .. ld - 1 are written as zeros.  std is a HOST array of at most MAPPO_MAX_STD_SLABS entries; n_std = 0 is
  * mappo_slab_copy; n_slabs = 0 (slabs may be NULL) only standardises -- the full pass over a field goes through here too, so
  * that slab and full pass are one piece of code (every operation IEEE, one explicit fused multiply-add per term of the
- * second moment) and bit-identical by construction. */
+ * second moment) and bit-identical to each other by construction (tests/test_gpu_standardize_at_insert.py). */
 #define MAPPO_MAX_STD_SLABS 4
 typedef struct mappo_std_slab {
     const float* src;

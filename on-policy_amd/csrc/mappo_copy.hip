@@ -21,8 +21,41 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxUnroll = 8;                    // independent loads per lane per pass (slab copy)
-constexpr unsigned kTileUnits = kThreads * kMaxUnroll;
+
+// The advantage normalisation (r_mappo.py:187): the two scalars read once, then an IEEE subtraction and division.
+struct AdvNorm {
+    float mean, den;
+    __device__ __forceinline__ float operator()(float v) const { return (v - mean) / den; }
+};
+__device__ __forceinline__ AdvNorm load_adv_norm(const float* stats, bool on) {
+    AdvNorm n = {0.f, 1.f};
+    if (on) {
+        n.mean = stats[0];
+        n.den = stats[1] + 1e-5f;
+    }
+    return n;
+}
+
+// Fills the row mapping of a gather and checks the ranges its 32-bit row arithmetic needs.
+int fill_row_map(mappo::RowMap& m, const int64_t* idx, int64_t mb, int chunked, int L, int T, int64_t N, int A) {
+    if (mb <= 0 || mb >= (1ll << 31)) return MAPPO_E_SHAPE;
+    if (chunked) {
+        if (L <= 0 || T <= 0 || N <= 0 || A <= 0) return MAPPO_E_SHAPE;
+        if ((long long)T * N * A >= (1ll << 31) || mb * (long long)L >= (1ll << 31)) return MAPPO_E_SHAPE;
+    }
+    m.idx = reinterpret_cast<const long long*>(idx);
+    m.mb = (unsigned)mb;
+    m.chunked = chunked;
+    m.L = (unsigned)(chunked ? L : 1);
+    m.T = (unsigned)T;
+    m.N = (unsigned)N;
+    m.A = (unsigned)A;
+    return 0;
+}
+
+// ------------------------------------------------------------- K3 / K4: gathers ----
+constexpr int kGatherLoads = 2;                  // independent loads per lane per pass
+constexpr unsigned kGatherTileUnits = kThreads * kGatherLoads;
 
 struct GField {
     const float* src;
@@ -54,51 +87,32 @@ template <> struct VecT<4> { using type = f32x4; };
 template <> struct VecT<2> { using type = f32x2; };
 template <> struct VecT<1> { using type = float; };
 
-__device__ __forceinline__ float norm1(float x, float mean, float den) { return (x - mean) / den; }
-__device__ __forceinline__ void normv(float& v, float m, float d) { v = norm1(v, m, d); }
-__device__ __forceinline__ void normv(f32x2& v, float m, float d) {
-    v.x = norm1(v.x, m, d);
-    v.y = norm1(v.y, m, d);
+__device__ __forceinline__ void normv(float& v, const AdvNorm& n) { v = n(v); }
+__device__ __forceinline__ void normv(f32x2& v, const AdvNorm& n) {
+    v.x = n(v.x);
+    v.y = n(v.y);
 }
-__device__ __forceinline__ void normv(f32x4& v, float m, float d) {
-    v.x = norm1(v.x, m, d);
-    v.y = norm1(v.y, m, d);
-    v.z = norm1(v.z, m, d);
-    v.w = norm1(v.w, m, d);
-}
-
-__device__ __forceinline__ unsigned source_row(const GatherArgs& a, const GField& fd, unsigned r) {
-    return mappo::source_row(a.map, fd.first_only, r);
+__device__ __forceinline__ void normv(f32x4& v, const AdvNorm& n) {
+    v.x = n(v.x);
+    v.y = n(v.y);
+    v.z = n(v.z);
+    v.w = n(v.w);
 }
 
-template <bool NT, typename V>
-__device__ __forceinline__ V ld(const V* p) {
-    return NT ? __builtin_nontemporal_load(p) : *p;
-}
-template <bool NT, typename V>
-__device__ __forceinline__ void st(V* p, V v) {
-    if (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-
-template <int VEC, int UNROLL, bool NT>
+// One tile: kGatherLoads non-temporal loads in flight per lane, then their non-temporal stores.
+template <int VEC>
 __device__ __forceinline__ void copy_tile(const GatherArgs& a, const GField& fd, unsigned tile_local) {
     using V = typename VecT<VEC>::type;
-    constexpr unsigned kPass = kThreads * UNROLL;
     const unsigned row0 = tile_local * fd.rows_per_tile;
     unsigned nrows = fd.rows_out - row0;
     if (nrows > fd.rows_per_tile) nrows = fd.rows_per_tile;
     const unsigned nunits = nrows * fd.upr;
-    float mean = 0.f, den = 1.f;
-    if (fd.normalize) {
-        mean = a.stats[0];
-        den = a.stats[1] + 1e-5f;  // r_mappo.py:187
-    }
-    for (unsigned i0 = 0; i0 < nunits; i0 += kPass) {
-        V val[UNROLL];
-        long long doff[UNROLL];
+    const AdvNorm norm = load_adv_norm(a.stats, fd.normalize != 0);
+    for (unsigned i0 = 0; i0 < nunits; i0 += kGatherTileUnits) {
+        V val[kGatherLoads];
+        long long doff[kGatherLoads];
 #pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
+        for (int u = 0; u < kGatherLoads; ++u) {
             unsigned i = i0 + u * kThreads + threadIdx.x;
             doff[u] = -1;
             val[u] = V(0.f);
@@ -106,23 +120,22 @@ __device__ __forceinline__ void copy_tile(const GatherArgs& a, const GField& fd,
                 unsigned r = (fd.upr == 1) ? i : __umulhi(i, fd.inv_upr);
                 unsigned w = i - r * fd.upr;
                 unsigned orow = row0 + r;
-                unsigned srow = source_row(a, fd, orow);
-                val[u] = ld<NT>(reinterpret_cast<const V*>(fd.src + (long long)srow * fd.width + w * VEC));
+                unsigned srow = mappo::source_row(a.map, fd.first_only, orow);
+                val[u] = __builtin_nontemporal_load(reinterpret_cast<const V*>(fd.src + (long long)srow * fd.width + w * VEC));
                 doff[u] = (long long)orow * fd.width + w * VEC;
             }
         }
 #pragma unroll
-        for (int u = 0; u < UNROLL; ++u) {
+        for (int u = 0; u < kGatherLoads; ++u) {
             if (doff[u] >= 0) {
                 V v = val[u];
-                if (fd.normalize) normv(v, mean, den);
-                st<NT>(reinterpret_cast<V*>(fd.dst + doff[u]), v);
+                if (fd.normalize) normv(v, norm);
+                __builtin_nontemporal_store(v, reinterpret_cast<V*>(fd.dst + doff[u]));
             }
         }
     }
 }
 
-template <int UNROLL, bool NT>
 __global__ void __launch_bounds__(kThreads) gather_kernel(GatherArgs a) {
     for (unsigned tile = blockIdx.x; tile < a.total_tiles; tile += gridDim.x) {
         int f = 0;
@@ -131,29 +144,29 @@ __global__ void __launch_bounds__(kThreads) gather_kernel(GatherArgs a) {
             if (tile >= a.f[k].tile_begin) f = k;
         const GField& fd = a.f[f];
         const unsigned tl = tile - fd.tile_begin;
-        if (fd.vec == 4) copy_tile<4, UNROLL, NT>(a, fd, tl);
-        else if (fd.vec == 2) copy_tile<2, UNROLL, NT>(a, fd, tl);
-        else copy_tile<1, UNROLL, NT>(a, fd, tl);
+        if (fd.vec == 4) copy_tile<4>(a, fd, tl);
+        else if (fd.vec == 2) copy_tile<2>(a, fd, tl);
+        else copy_tile<1>(a, fd, tl);
     }
 }
 
-int g_gather_variant = 5;  // default: 2 loads in flight per lane, non-temporal.  bits 0-1: log2(unroll), bit 2: nontemporal, bits 4+: blocks per CU (0 = occupancy)
+int g_gather_variant = 5;  // mappo_gather_set_variant: only bits 4+ are read, the workgroups per CU (0 = occupancy)
 
-template <int UNROLL, bool NT>
-hipError_t launch_gather(const GatherArgs& a, unsigned tile_units, int blocks_per_cu, hipStream_t stream) {
-    static int occ = 0;  // resident workgroups per CU for this instantiation
+hipError_t launch_gather(const GatherArgs& a, hipStream_t stream) {
+    static int occ = 0;  // resident workgroups per CU
     if (occ == 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gather_kernel<UNROLL, NT>, kThreads, 0) != hipSuccess || n <= 0)
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gather_kernel, kThreads, 0) != hipSuccess || n <= 0)
             n = 4;
         occ = n;
     }
     // a persistent grid: exactly the resident workgroups (a second, partial wave of workgroups
     // would run at reduced occupancy), each walking the tile list with stride gridDim.x
+    const int blocks_per_cu = g_gather_variant >> 4;
     int per_cu = blocks_per_cu > 0 ? blocks_per_cu : occ;
     unsigned grid = (unsigned)(mappo::kCUs * per_cu);
     if (a.total_tiles < grid) grid = a.total_tiles;
-    hipLaunchKernelGGL((gather_kernel<UNROLL, NT>), dim3(grid), dim3(kThreads), 0, stream, a);
+    hipLaunchKernelGGL(gather_kernel, dim3(grid), dim3(kThreads), 0, stream, a);
     return hipGetLastError();
 }
 
@@ -161,26 +174,11 @@ int build_and_launch(const mappo_field_t* fields, int n_fields, const int64_t* i
                      int chunked, int L, int T, int64_t N, int A, const float* stats,
                      hipStream_t stream) {
     if (!fields || !idx) return MAPPO_E_NULL;
-    if (n_fields <= 0 || mb <= 0) return MAPPO_E_SHAPE;
+    if (n_fields <= 0) return MAPPO_E_SHAPE;
     if (n_fields > MAPPO_MAX_FIELDS) return MAPPO_E_TOO_MANY;
-    if (mb >= (1ll << 31)) return MAPPO_E_SHAPE;
-    if (chunked) {
-        if (L <= 0 || T <= 0 || N <= 0 || A <= 0) return MAPPO_E_SHAPE;
-        if ((long long)T * N * A >= (1ll << 31) || mb * (long long)L >= (1ll << 31)) return MAPPO_E_SHAPE;
-    }
-    const int variant = g_gather_variant;
-    const int unroll = 1 << (variant & 3);
-    const bool nt = (variant & 4) != 0;
-    const int blocks_per_cu = variant >> 4;
-    const unsigned tile_units = (unsigned)(kThreads * unroll);
     GatherArgs a;
-    a.map.idx = reinterpret_cast<const long long*>(idx);
-    a.map.mb = (unsigned)mb;
-    a.map.chunked = chunked;
-    a.map.L = (unsigned)L;
-    a.map.T = (unsigned)T;
-    a.map.N = (unsigned)N;
-    a.map.A = (unsigned)A;
+    int rc = fill_row_map(a.map, idx, mb, chunked, L, T, N, A);
+    if (rc != 0) return rc;
     a.stats = stats;
     unsigned long long tiles = 0;
     int nf = 0;
@@ -194,7 +192,7 @@ int build_and_launch(const mappo_field_t* fields, int n_fields, const int64_t* i
             // row-standardised fields go through the row-owning kernel (it needs whole-row statistics)
             const unsigned fo = (chunked && s.first_only) ? 1u : 0u;
             const long long rows = (chunked && !fo) ? mb * (long long)L : mb;
-            int rc = mappo::gather_standardize(s.src, s.dst, s.width, rows, a.map, fo, 1e-5f, stream);
+            rc = mappo::gather_standardize(s.src, s.dst, s.width, rows, a.map, fo, 1e-5f, stream);
             if (rc != 0) return rc;
             continue;
         }
@@ -204,7 +202,7 @@ int build_and_launch(const mappo_field_t* fields, int n_fields, const int64_t* i
         g.width = (unsigned)s.width;
         g.vec = (unsigned)mappo::row_vec(s.src, s.dst, s.width);
         g.upr = g.width / g.vec;
-        g.rows_per_tile = g.upr >= tile_units ? 1u : tile_units / g.upr;
+        g.rows_per_tile = g.upr >= kGatherTileUnits ? 1u : kGatherTileUnits / g.upr;
         g.inv_upr = (unsigned)(((1ull << 32) + g.upr - 1) / g.upr);
         g.first_only = (chunked && s.first_only) ? 1u : 0u;
         g.normalize = s.normalize ? 1u : 0u;
@@ -217,18 +215,7 @@ int build_and_launch(const mappo_field_t* fields, int n_fields, const int64_t* i
     a.nf = nf;
     a.total_tiles = (unsigned)tiles;
     if (nf == 0) return 0;
-    hipError_t e;
-    switch ((variant & 3) | (nt ? 4 : 0)) {
-        case 0: e = launch_gather<1, false>(a, tile_units, blocks_per_cu, stream); break;
-        case 1: e = launch_gather<2, false>(a, tile_units, blocks_per_cu, stream); break;
-        case 2: e = launch_gather<4, false>(a, tile_units, blocks_per_cu, stream); break;
-        case 3: e = launch_gather<8, false>(a, tile_units, blocks_per_cu, stream); break;
-        case 4: e = launch_gather<1, true>(a, tile_units, blocks_per_cu, stream); break;
-        case 5: e = launch_gather<2, true>(a, tile_units, blocks_per_cu, stream); break;
-        case 6: e = launch_gather<4, true>(a, tile_units, blocks_per_cu, stream); break;
-        default: e = launch_gather<8, true>(a, tile_units, blocks_per_cu, stream); break;
-    }
-    return (int)e;
+    return (int)launch_gather(a, stream);
 }
 
 // ------------------------------------------------ packed records of the narrow fields ----
@@ -261,8 +248,6 @@ __global__ void __launch_bounds__(kThreads) pack_records_kernel(RecArgs a) {
     const unsigned rw = a.rw;
     for (unsigned long long row0 = (unsigned long long)blockIdx.x * kThreads; row0 < a.rows;
          row0 += (unsigned long long)gridDim.x * kThreads) {
-        const unsigned long long row = row0 + threadIdx.x;
-        const bool ok = row < a.rows;
         for (unsigned c = threadIdx.x; c < kThreads * rw; c += kThreads) tile[c] = 0.f;
         __syncthreads();
         for (int k = 0; k < a.nf; ++k) {
@@ -280,7 +265,6 @@ __global__ void __launch_bounds__(kThreads) pack_records_kernel(RecArgs a) {
         for (unsigned e = threadIdx.x; e < kThreads * rw; e += kThreads)
             if (base + e < limit) a.records[base + e] = tile[e];
         __syncthreads();
-        (void)ok;
     }
 }
 
@@ -295,11 +279,7 @@ __global__ void __launch_bounds__(kThreads) gather_records_kernel(RecArgs a, uns
     const unsigned rounds = (kThreads * kRecMaxWidth / rw) / per_round;
     const unsigned pass_rows = per_round * rounds;                // rows per pass: what the LDS tile holds
     const unsigned sub = threadIdx.x / q4, piece = threadIdx.x - sub * q4;
-    float mean = 0.f, den = 1.f;
-    if (a.stats) {
-        mean = a.stats[0];
-        den = a.stats[1] + 1e-5f;
-    }
+    const AdvNorm adv = load_adv_norm(a.stats, a.stats != nullptr);
     for (unsigned long long row0 = (unsigned long long)blockIdx.x * pass_rows; row0 < rows_out;
          row0 += (unsigned long long)gridDim.x * pass_rows) {
         if (sub < per_round) {
@@ -323,7 +303,7 @@ __global__ void __launch_bounds__(kThreads) gather_records_kernel(RecArgs a, uns
             for (unsigned e = threadIdx.x; e < nrows * w; e += kThreads) {
                 unsigned r = e / w, c = e - r * w;
                 float v = tile[r * rw + off + c];
-                if (norm) v = (v - mean) / den;
+                if (norm) v = adv(v);
                 dst[row0 * w + e] = v;
             }
         }
@@ -351,6 +331,9 @@ int fill_rec_args(RecArgs& a, const mappo_record_field_t* fields, int n_fields, 
 }
 
 // ------------------------------------------------------------------ K2: slabs ----
+constexpr int kSlabLoads = 8;                    // independent loads per lane per tile
+constexpr unsigned kSlabTileUnits = kThreads * kSlabLoads;
+
 struct Slab {
     const float* src;
     float* dst;
@@ -364,8 +347,9 @@ struct SlabArgs {
     unsigned total_tiles;
 };
 
-__global__ void __launch_bounds__(kThreads) slab_kernel(SlabArgs a) {
-    for (unsigned tile = blockIdx.x; tile < a.total_tiles; tile += gridDim.x) {
+// The slab copy loop: workgroup `block` of `nblocks` walks the tile list with stride nblocks.
+__device__ __forceinline__ void copy_tiles(const SlabArgs& a, unsigned block, unsigned nblocks) {
+    for (unsigned tile = block; tile < a.total_tiles; tile += nblocks) {
         int k = 0;
 #pragma unroll 1
         for (int q = 1; q < a.n; ++q)
@@ -376,55 +360,40 @@ __global__ void __launch_bounds__(kThreads) slab_kernel(SlabArgs a) {
         float* s_dst = a.s[k].dst;
         const unsigned long long units = a.s[k].units;
         const unsigned vec = a.s[k].vec;
-        unsigned long long base = (unsigned long long)(tile - a.s[k].tile_begin) * kTileUnits;
+        unsigned long long base = (unsigned long long)(tile - a.s[k].tile_begin) * kSlabTileUnits;
         if (vec == 4) {
             const float4* src = reinterpret_cast<const float4*>(s_src);
             float4* dst = reinterpret_cast<float4*>(s_dst);
-            float4 v[kMaxUnroll];
+            float4 v[kSlabLoads];
 #pragma unroll
-            for (int u = 0; u < kMaxUnroll; ++u) {
+            for (int u = 0; u < kSlabLoads; ++u) {
                 unsigned long long i = base + u * kThreads + threadIdx.x;
                 v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (i < units) v[u] = src[i];
             }
 #pragma unroll
-            for (int u = 0; u < kMaxUnroll; ++u) {
+            for (int u = 0; u < kSlabLoads; ++u) {
                 unsigned long long i = base + u * kThreads + threadIdx.x;
                 if (i < units) dst[i] = v[u];
             }
         } else {
-            const float* src = s_src;
-            float* dst = s_dst;
-            float v[kMaxUnroll];
+            float v[kSlabLoads];
 #pragma unroll
-            for (int u = 0; u < kMaxUnroll; ++u) {
+            for (int u = 0; u < kSlabLoads; ++u) {
                 unsigned long long i = base + u * kThreads + threadIdx.x;
                 v[u] = 0.f;
-                if (i < units) v[u] = src[i];
+                if (i < units) v[u] = s_src[i];
             }
 #pragma unroll
-            for (int u = 0; u < kMaxUnroll; ++u) {
+            for (int u = 0; u < kSlabLoads; ++u) {
                 unsigned long long i = base + u * kThreads + threadIdx.x;
-                if (i < units) dst[i] = v[u];
+                if (i < units) s_dst[i] = v[u];
             }
         }
     }
 }
 
-}  // namespace
-
-extern "C" int mappo_gather_rows(const mappo_field_t* fields, int n_fields, const int64_t* idx,
-                                 int64_t mb, const float* stats, mappo_stream_t stream) {
-    return build_and_launch(fields, n_fields, idx, mb, 0, 1, 1, 1, 1, stats,
-                            static_cast<hipStream_t>(stream));
-}
-
-extern "C" int mappo_gather_chunks(const mappo_field_t* fields, int n_fields, const int64_t* idx,
-                                   int64_t mb, int L, int T, int64_t N, int A, const float* stats,
-                                   mappo_stream_t stream) {
-    return build_and_launch(fields, n_fields, idx, mb, 1, L, T, N, A, stats,
-                            static_cast<hipStream_t>(stream));
-}
+__global__ void __launch_bounds__(kThreads) slab_kernel(SlabArgs a) { copy_tiles(a, blockIdx.x, gridDim.x); }
 
 // ---- K2 with the standardised copies of the observation slabs kept current in the SAME launch (round 6) ----
 // insert / chooseinsert / after_update write one slab per field; networks with an input LayerNorm read the observation fields
@@ -513,49 +482,6 @@ __device__ void standardize_slab(const StdSlab& d, unsigned block, unsigned nblo
     }
 }
 
-__device__ __forceinline__ void copy_tiles(const SlabArgs& a, unsigned block, unsigned nblocks) {
-    for (unsigned tile = block; tile < a.total_tiles; tile += nblocks) {
-        int k = 0;
-#pragma unroll 1
-        for (int q = 1; q < a.n; ++q)
-            if (tile >= a.s[q].tile_begin) k = q;
-        const float* s_src = a.s[k].src;
-        float* s_dst = a.s[k].dst;
-        const unsigned long long units = a.s[k].units;
-        const unsigned vec = a.s[k].vec;
-        unsigned long long base = (unsigned long long)(tile - a.s[k].tile_begin) * kTileUnits;
-        if (vec == 4) {
-            const float4* src = reinterpret_cast<const float4*>(s_src);
-            float4* dst = reinterpret_cast<float4*>(s_dst);
-            float4 v[kMaxUnroll];
-#pragma unroll
-            for (int u = 0; u < kMaxUnroll; ++u) {
-                unsigned long long i = base + u * kThreads + threadIdx.x;
-                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (i < units) v[u] = src[i];
-            }
-#pragma unroll
-            for (int u = 0; u < kMaxUnroll; ++u) {
-                unsigned long long i = base + u * kThreads + threadIdx.x;
-                if (i < units) dst[i] = v[u];
-            }
-        } else {
-            float v[kMaxUnroll];
-#pragma unroll
-            for (int u = 0; u < kMaxUnroll; ++u) {
-                unsigned long long i = base + u * kThreads + threadIdx.x;
-                v[u] = 0.f;
-                if (i < units) v[u] = s_src[i];
-            }
-#pragma unroll
-            for (int u = 0; u < kMaxUnroll; ++u) {
-                unsigned long long i = base + u * kThreads + threadIdx.x;
-                if (i < units) s_dst[i] = v[u];
-            }
-        }
-    }
-}
-
 __global__ void __launch_bounds__(kThreads) slab_std_kernel(SlabArgs a, StdArgs st) {
     if (blockIdx.x < st.copy_blocks) {
         copy_tiles(a, blockIdx.x, st.copy_blocks);
@@ -577,7 +503,6 @@ __global__ void __launch_bounds__(kThreads) slab_std_kernel(SlabArgs a, StdArgs 
     standardize_slab(d, b - st.s[k].block_begin, st.s[k].blocks);
 }
 
-namespace {
 int fill_slabs(const mappo_slab_t* slabs, int n_slabs, SlabArgs& a) {
     if (!slabs) return MAPPO_E_NULL;
     if (n_slabs <= 0) return MAPPO_E_SHAPE;
@@ -595,13 +520,27 @@ int fill_slabs(const mappo_slab_t* slabs, int n_slabs, SlabArgs& a) {
         d.vec = (unsigned)(mappo::row_vec(s.src, s.dst, s.count) == 4 ? 4 : 1);
         d.units = (unsigned long long)s.count / d.vec;
         d.tile_begin = (unsigned)tiles;
-        tiles += (d.units + kTileUnits - 1) / kTileUnits;
+        tiles += (d.units + kSlabTileUnits - 1) / kSlabTileUnits;
         if (tiles >= (1ull << 32)) return MAPPO_E_SHAPE;
     }
     a.total_tiles = (unsigned)tiles;
     return 0;
 }
+
 }  // namespace
+
+extern "C" int mappo_gather_rows(const mappo_field_t* fields, int n_fields, const int64_t* idx,
+                                 int64_t mb, const float* stats, mappo_stream_t stream) {
+    return build_and_launch(fields, n_fields, idx, mb, 0, 1, 1, 1, 1, stats,
+                            static_cast<hipStream_t>(stream));
+}
+
+extern "C" int mappo_gather_chunks(const mappo_field_t* fields, int n_fields, const int64_t* idx,
+                                   int64_t mb, int L, int T, int64_t N, int A, const float* stats,
+                                   mappo_stream_t stream) {
+    return build_and_launch(fields, n_fields, idx, mb, 1, L, T, N, A, stats,
+                            static_cast<hipStream_t>(stream));
+}
 
 extern "C" int mappo_slab_copy(const mappo_slab_t* slabs, int n_slabs, mappo_stream_t stream) {
     SlabArgs a;
@@ -675,14 +614,12 @@ extern "C" int mappo_gather_records(const float* records, int record_width, cons
                                     int n_fields, const int64_t* idx, int64_t mb, int L, int T, int64_t N,
                                     int A, const float* stats, mappo_stream_t stream) {
     if (!records || !idx) return MAPPO_E_NULL;
-    if (mb <= 0 || mb >= (1ll << 31)) return MAPPO_E_SHAPE;
-    if (!mappo::aligned_to(records, 16)) return MAPPO_E_ALIGN;
-    const int chunked = L > 0 ? 1 : 0;
-    if (chunked && (T <= 0 || N <= 0 || A <= 0 || (long long)T * N * A >= (1ll << 31) ||
-                    mb * (long long)L >= (1ll << 31)))
-        return MAPPO_E_SHAPE;
     RecArgs a;
-    int rc = fill_rec_args(a, fields, n_fields, record_width, false);
+    const int chunked = L > 0 ? 1 : 0;
+    int rc = fill_row_map(a.map, idx, mb, chunked, L, T, N, A);
+    if (rc != 0) return rc;
+    if (!mappo::aligned_to(records, 16)) return MAPPO_E_ALIGN;
+    rc = fill_rec_args(a, fields, n_fields, record_width, false);
     if (rc != 0) return rc;
     bool any_norm = false;
     for (int k = 0; k < n_fields; ++k) any_norm = any_norm || fields[k].normalize;
@@ -690,13 +627,6 @@ extern "C" int mappo_gather_records(const float* records, int record_width, cons
     a.records = const_cast<float*>(records);
     a.rows = 0;
     a.stats = any_norm ? stats : nullptr;
-    a.map.idx = reinterpret_cast<const long long*>(idx);
-    a.map.mb = (unsigned)mb;
-    a.map.chunked = chunked;
-    a.map.L = (unsigned)(chunked ? L : 1);
-    a.map.T = (unsigned)T;
-    a.map.N = (unsigned)N;
-    a.map.A = (unsigned)A;
     const unsigned long long rows_out = chunked ? (unsigned long long)mb * L : (unsigned long long)mb;
     long long blocks = (long long)((rows_out + kThreads - 1) / kThreads);
     if (blocks > mappo::kCUs * 5) blocks = mappo::kCUs * 5;     // 32 KB of LDS per workgroup: 5 per CU

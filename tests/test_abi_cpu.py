@@ -66,6 +66,8 @@ def test_argument_validation_without_device():
     assert lib.mappo_adv_reduce(None, 1, None, None) == -1
     assert lib.mappo_gather_rows(None, 1, None, 1, None, None) == -1
     assert lib.mappo_slab_copy(None, 1, None) == -1
+    old = lib.mappo_gather_set_variant(21)      # the hook hands back what it held
+    assert lib.mappo_gather_set_variant(old) == 21
     assert lib.mappo_gae_partial_rows(0) == 0
     assert lib.mappo_gae_partial_rows(32768) == 2048
     assert lib.mappo_error_string(-2).decode().startswith("a size")

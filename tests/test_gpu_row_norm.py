@@ -23,11 +23,9 @@ import torch
 
 import loss_reference as lr
 import row_norm_cases as rn
+from carved import DEV, NAN_BITS, Carved, chunk_map as _chunk_map
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda", 0)
-PAD = 64                            # canary floats in front of and behind every carved operand (a multiple of 4)
-NAN_BITS = 0x7FC00000               # torch.full(nan)
 E_NULL, E_SHAPE, E_FLAGS = -1, -2, -3
 JUDGE = lr.Judge()
 # floors of the 4 x judge: ~3 x the largest kernel error measured on the MI355X, never above 1e-5 (module docstring)
@@ -74,26 +72,6 @@ def _stream():
 
 def _tag(shape):
     return "v%d.l%d.e%d" % shape
-
-
-class Carved(object):
-    """``n`` floats inside a NaN-filled buffer, ``off`` floats past a 16-byte boundary, PAD canary floats either side."""
-
-    def __init__(self, n, off=0, values=None):
-        self.buf = torch.full((PAD + off + n + PAD,), float("nan"), device=DEV)
-        assert self.buf.data_ptr() % 16 == 0
-        self.lo, self.n = PAD + off, n
-        self.t = self.buf[self.lo:self.lo + n]
-        assert self.t.data_ptr() % 16 == 4 * (off % 4)
-        if values is not None:
-            self.t.copy_(values.reshape(-1))
-
-    def ptr(self):
-        return self.t.data_ptr()
-
-    def intact(self):
-        bits = self.buf.view(torch.int32)
-        return bool((bits[:self.lo] == NAN_BITS).all()) and bool((bits[self.lo + self.n:] == NAN_BITS).all())
 
 
 def _ptr(c):
@@ -293,14 +271,6 @@ def _gather(src, dst, idx, mb, D, chunk=None, first=None):
         rc = _lib().mappo_gather_chunks(fields, n, idx.data_ptr(), mb, chunk["L"], chunk["T"], chunk["N"], chunk["A"], None,
                                         _stream())
     assert rc == 0, rc
-
-
-def _chunk_map(idx, mb, L, T, N, A, first_only=False):
-    """Source row of every output row (l, j) -> l * mb + j: include/mappo_hip.h, mappo_gather_chunks."""
-    ls = torch.zeros(1, dtype=torch.int64, device=DEV) if first_only else torch.arange(L, device=DEV)
-    f = (idx[None, :] * L + ls[:, None]).reshape(-1)
-    n, rem = f // (A * T), f % (A * T)
-    return ((rem % T) * N + n) * A + rem // T
 
 
 def _judge_gather(tag, src, dst, rows_map, D, what):

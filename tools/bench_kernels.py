@@ -48,7 +48,8 @@ def main():
     ap.add_argument("--N", type=int, default=4096)
     ap.add_argument("--A", type=int, default=8)
     ap.add_argument("--variants", default="0,3036,3054,3056,57,3057,99")
-    ap.add_argument("--gather-variants", default="1,5,2,3,113,133,69,101")
+    ap.add_argument("--gather-variants", default="5,21,37,69,133",
+                    help="mappo_gather_set_variant values: 5 | (workgroups per CU << 4), 0 workgroups = occupancy")
     ap.add_argument("--sets", type=int, default=6)
     ap.add_argument("--iters", type=int, default=24)
     ap.add_argument("--gather-N", type=int, default=1024)
@@ -172,7 +173,9 @@ def main():
         perms = [torch.randperm(B, device=dev) for _ in range(2)]
         combos = [("all_fields", list(widths)), ("share_obs_only", ["share_obs"]),
                   ("scalars_only", ["actions", "value_preds", "returns", "masks", "active_masks", "logp", "adv"])]
-        for gv in [int(v) for v in opt.gather_variants.split(",")]:
+        gvs = [int(v) for v in opt.gather_variants.split(",")]
+        default_gv = lib.mappo_gather_set_variant(gvs[0])     # the library's own value: the headline figures run on it
+        for gv in gvs:
             lib.mappo_gather_set_variant(gv)
             for label, names in combos[:2]:
                 fields = (_native.Field * len(names))(*[
@@ -186,7 +189,7 @@ def main():
                 nbytes = sum(2 * 4 * widths[k] for k in names) * B + 8 * B
                 gres["gv%d_%s" % (gv, label)] = {"ms": t["median_us"] / 1e3,
                                                  "GBps": nbytes / (t["median_us"] * 1e-6) / 1e9}
-        lib.mappo_gather_set_variant(0)
+        lib.mappo_gather_set_variant(default_gv)
         for label, names in combos:
             fields = (_native.Field * len(names))(*[
                 _native.Field(src[k].data_ptr(), dst[k].data_ptr(), widths[k], 0, 1 if k == "adv" else 0, 0)
