@@ -732,7 +732,10 @@ int     mappo_mlp_set_debug(long long* buf);
  * 128 = under MAPPO_ARITH_SIX_TERM the version-4 forward (first layer in six-term form, one wave per SIMD) also for aligned inputs narrower than 128 floats,
  * which by default take version 3 with only the hidden layer in six-term form (tests: every chunk shape of version 4);
  * 256 = under MAPPO_ARITH_SIX_TERM two-layer trunks with aligned inputs of at most 64 columns keep the separate first-layer
- * weight-gradient kernel (mlp_dw1_rows_kernel) instead of accumulating that gradient inside the chain's launch (A/B, tests). */
+ * weight-gradient kernel (mlp_dw1_rows_kernel) instead of accumulating that gradient inside the chain's launch (A/B, tests);
+ * 16384 = under MAPPO_ARITH_SIX_TERM the two-slot direct first-layer weight-gradient kernel of inputs up to 384 floats wide
+ * lets every wave split the whole dz1 tile into bf16 planes itself (default: once per workgroup, every wave its own four rows,
+ * the planes shared through LDS); the same bits either way (A/B, tests). */
 int     mappo_mlp_set_flags(int flags);
 int     mappo_mlp_forward(const mappo_mlp_t* net, mappo_stream_t stream);
 int     mappo_mlp_backward(const mappo_mlp_t* net, mappo_stream_t stream);

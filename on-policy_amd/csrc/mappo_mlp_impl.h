@@ -1181,25 +1181,31 @@ __device__ __forceinline__ void split3(const float* x, bf8& p1, bf8& p2, bf8& p3
 // Two values at a time: one v_cvt_pk_bf16_f32 per plane and pair, whose halves are widened again by a shift and a mask
 // (the pair is pinned as ONE register so that the compiler does not convert each value a second time on its own).
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void split3_pair(float x0, float x1, bf2& q1, bf2& q2, bf2& q3) {
+    q1 = bf2{(__bf16)x0, (__bf16)x1};
+    MAPPO_SINGLE_ISSUE(q1);
+    float r0 = x0 - (float)q1[0], r1 = x1 - (float)q1[1];
+    MAPPO_SINGLE_ISSUE(r0);
+    MAPPO_SINGLE_ISSUE(r1);
+    q2 = bf2{(__bf16)r0, (__bf16)r1};
+    MAPPO_SINGLE_ISSUE(q2);
+    float t0 = r0 - (float)q2[0], t1 = r1 - (float)q2[1];
+    MAPPO_SINGLE_ISSUE(t0);
+    MAPPO_SINGLE_ISSUE(t1);
+    q3 = bf2{(__bf16)t0, (__bf16)t1};
+}
 __device__ __forceinline__ void split3_single(const float* x, bf8& p1, bf8& p2, bf8& p3) {
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
-        bf2 q1 = {(__bf16)x[e], (__bf16)x[e + 1]};
-        MAPPO_SINGLE_ISSUE(q1);
-        float r0 = x[e] - (float)q1[0], r1 = x[e + 1] - (float)q1[1];
-        MAPPO_SINGLE_ISSUE(r0);
-        MAPPO_SINGLE_ISSUE(r1);
-        bf2 q2 = {(__bf16)r0, (__bf16)r1};
-        MAPPO_SINGLE_ISSUE(q2);
-        float t0 = r0 - (float)q2[0], t1 = r1 - (float)q2[1];
-        MAPPO_SINGLE_ISSUE(t0);
-        MAPPO_SINGLE_ISSUE(t1);
+        bf2 q1, q2, q3;
+        split3_pair(x[e], x[e + 1], q1, q2, q3);
         p1[e] = q1[0];
         p1[e + 1] = q1[1];
         p2[e] = q2[0];
         p2[e + 1] = q2[1];
-        p3[e] = (__bf16)t0;
-        p3[e + 1] = (__bf16)t1;
+        p3[e] = q3[0];
+        p3[e + 1] = q3[1];
     }
 }
 
@@ -2497,6 +2503,7 @@ struct Dw1Args {
     const float* dz1;
     float* partials;    // [gridDim.x][64 * din]
     long long* dbg;     // tuning hook (mappo_mlp_set_debug): cycle stamps of workgroup 0's first tiles at [512 ...], or NULL
+    int flags;          // option bits (mappo_mlp_set_flags); 16384: every wave splits the whole dz1 tile itself
 };
 constexpr int kDw1StageX = kDw1Rows * kDw1Slab;                        // floats
 constexpr int kDw1Stage = kDw1StageX + kDw1Rows * 64;                  // + dz1 tile [32][64]
@@ -2678,6 +2685,8 @@ constexpr int d2_lds_slots(int maxnt, int slots) { return 4 * slots * d2_xslot(m
 constexpr int d2_lds(int maxnt) { return d2_lds_slots(maxnt, kD2Slots); }   // floats, + the row-table rings:
 constexpr int kD2TabRing = 2 * kD2Slots;         // 256-byte slots per wave
 inline int d2_maxnt(int din) { return (din + 511) / 512 < (din + 383) / 384 ? 4 : 3; }
+// the instance that splits the dz1 tile once per workgroup (dw1_tile_steps6): + a third dz1 slot and two plane buffers
+constexpr bool dw1_shares_planes(int maxnt, int slots, bool six) { return six && maxnt == 3 && slots == 2; }
 
 // the 8 MFMA steps of one 16-row tile (step s contracts rows s and 8 + s) for a wave that owns NT k tiles
 template <int NT>
@@ -2714,14 +2723,54 @@ __device__ __forceinline__ void dw1_tile_steps(const float* xt, const float* dzt
 // rows 8 g .. 8 g + 7 of its column (dz1: feature c / 32 + c; x: column c of each k tile), read from the row-major LDS tiles
 // with the same strided 4-byte reads as above, split into three bf16 planes in the wave, six terms per float32 product,
 // smallest first: 36 MFMAs of 8 passes per tile (NT = 3) instead of 48 of 16 passes, + ~180 split instructions.
-template <int NT>
-__device__ __forceinline__ void dw1_tile_steps6(const float* xt, const float* dzt, int c, int h, f32x16 (*acc)[2]) {
-    if (NT == 0) return;
-    float a0[8], a1[8];
+//
+// SHARE (the two-slot, three-k-tile instance): the dz1 tile is split ONCE per workgroup.  All four waves need the same six A
+// operands, and splitting the whole tile in every wave was ~90 vector instructions and 16 strided LDS reads of serial prefix
+// per tile.  Wave w splits only the rows it fetched (4 w .. 4 w + 3, lane = feature: four values) and stores the three
+// planes, 8 bytes each, into its half of the A-operand pieces of a plane buffer [plane 3][feature tile 2][lane 64] x 16
+// bytes; after the tile's barrier every wave reads its six operands as six 16-byte pieces.  The share of tile m + 1 is
+// split under the MFMAs of tile m's last k tile, so none of it stands before the barrier.  split3_pair is split3 value for
+// value and the terms keep their order: the sums are bit for bit those of the per-wave split.
+struct Dw1Share {
+    const float* src;   // this lane's feature in the wave's quarter of the NEXT tile's dz1 slot (row j at + 64 j)
+    float* dst;         // this lane's 8 bytes of plane 0 in the next tile's plane buffer (plane p at + kD2PlaneFloats p)
+    int live;           // rows of that quarter inside the launch (<= 0: none); the others count as zero
+};
+constexpr int kD2PlaneFloats = 2 * 64 * 4;                  // one plane of the A operands: [feature tile 2][64 lanes] x 16 bytes
+constexpr int kD2PlaneBuf = 3 * kD2PlaneFloats;             // floats per plane buffer (6 KB); two buffers
+__device__ __forceinline__ void dw1_share_planes(const float* q, float* dst) {
+    bf2 p[2][3];
+    split3_pair(q[0], q[1], p[0][0], p[0][1], p[0][2]);
+    split3_pair(q[2], q[3], p[1][0], p[1][1], p[1][2]);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        a0[e] = dzt[(8 * h + e) * 64 + c];
-        a1[e] = dzt[(8 * h + e) * 64 + 32 + c];
+    for (int k = 0; k < 3; ++k)
+        *reinterpret_cast<bf4*>(dst + k * kD2PlaneFloats) = bf4{p[0][k][0], p[0][k][1], p[1][k][0], p[1][k][1]};
+}
+
+// planes: the tile's plane buffer, or NULL: split the dz1 tile dzt in this wave
+template <int NT, bool SHARE = false>
+__device__ __forceinline__ void dw1_tile_steps6(const float* xt, const float* dzt, int c, int h, f32x16 (*acc)[2],
+                                                const float* planes = nullptr, const Dw1Share* sh = nullptr) {
+    float q[4];
+    if (SHARE) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float v = sh->src[64 * j];
+            q[j] = j < sh->live ? v : 0.f;
+        }
+    }
+    if (NT == 0) {
+        if (SHARE) dw1_share_planes(q, sh->dst);
+        return;
+    }
+    const bool own_split = !SHARE || planes == nullptr;
+    float a0[8], a1[8];
+    if (own_split) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            a0[e] = dzt[(8 * h + e) * 64 + c];
+            a1[e] = dzt[(8 * h + e) * 64 + 32 + c];
+        }
     }
     float b[NT > 0 ? NT : 1][8];
 #pragma unroll
@@ -2729,15 +2778,25 @@ __device__ __forceinline__ void dw1_tile_steps6(const float* xt, const float* dz
 #pragma unroll
         for (int e = 0; e < 8; ++e) b[i][e] = xt[i * (kD2Rows * 32) + (8 * h + e) * 32 + c];
     bf8 A[2][3], Bn[3];
-    split3(a0, A[0][0], A[0][1], A[0][2]);
-    split3(a1, A[1][0], A[1][1], A[1][2]);
+    if (own_split) {
+        split3(a0, A[0][0], A[0][1], A[0][2]);
+        split3(a1, A[1][0], A[1][1], A[1][2]);
+    } else {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                A[t][k] = *reinterpret_cast<const bf8*>(planes + k * kD2PlaneFloats + t * 256 + 4 * (32 * h + c));
+    }
     split3(b[0], Bn[0], Bn[1], Bn[2]);
-    // (k tile i + 1's x is split while k tile i's 12 MFMAs run: four of its ~45 vector instructions per MFMA gap)
+    // (k tile i + 1's x is split while k tile i's 12 MFMAs run: four of its ~45 vector instructions per MFMA gap; the
+    // last k tile's gaps take the next tile's dz1 share)
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
         const bf8 B[3] = {Bn[0], Bn[1], Bn[2]};
         prim::sched_fence();
         if (i + 1 < NT) split3_single(b[i + 1 < NT ? i + 1 : 0], Bn[0], Bn[1], Bn[2]);
+        else if (SHARE) dw1_share_planes(q, sh->dst);
         acc[i][0] = prim::mfma_bf16(A[0][0], B[2], acc[i][0]);
         acc[i][1] = prim::mfma_bf16(A[1][0], B[2], acc[i][1]);
         acc[i][0] = prim::mfma_bf16(A[0][2], B[0], acc[i][0]);
@@ -2754,43 +2813,107 @@ __device__ __forceinline__ void dw1_tile_steps6(const float* xt, const float* dz
             MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4);
             MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4);
             MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4); MAPPO_MFMA_GAP(0, 4);
+        } else if (SHARE) {
+            MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3);
+            MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3);
+            MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3); MAPPO_MFMA_GAP(0, 3);
         }
     }
 }
 
-// the whole kernel for a wave that owns NT (0 .. MAXNT) k tiles: tiles wave, wave + 4, wave + 8 (, wave + 12) of the slab
-template <int NT, int MAXNT, int SLOTS, bool SIX = false>
-__device__ __forceinline__ void dw1_direct_body(const Dw1Args& a, float* lds, int wave, int k0) {
-    // SLOTS = 4: one workgroup per CU, the loads of tile m + 3 in flight; SLOTS = 2: half the LDS, two workgroups per CU
-    // (two waves per SIMD), the loads of tile m + 1 in flight -- the other workgroup's MFMA stream covers the wait
-    constexpr int kD2Slots = SLOTS, kD2TabRing = 2 * SLOTS;
-    constexpr int kD2XSlot = d2_xslot(MAXNT), kD2Lds = d2_lds_slots(MAXNT, SLOTS);
-    const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, h = lane >> 5;
-    const int din = a.rs.din;
-    const long long rows = a.rs.rows;
-    const long long ntiles = (rows + kD2Rows - 1) / kD2Rows;
-    const long long n_it = blockIdx.x < ntiles ? (ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
-    float* xs = lds + wave * kD2Slots * kD2XSlot;           // this wave's slots
-    float* dzs = lds + 4 * kD2Slots * kD2XSlot;             // the workgroup's dz1 slots
-    constexpr int G = 2 * NT + 2;                           // loads per group
+// What the tile loop needs whatever number of k tiles the wave owns: the workgroup's tiles, the LDS rings and their loads.
+// SLOTS = 4: one workgroup per CU, the loads of tile m + 3 in flight; SLOTS = 2: half the LDS, two workgroups per CU
+// (two waves per SIMD), the loads of tile m + 1 in flight -- the other workgroup's MFMA stream covers the wait.
+// kShareable (six terms, two slots, three k tiles): the dz1 tile's bf16 planes are made once per workgroup (see
+// dw1_tile_steps6) unless option bit 16384 asks for the per-wave split.  A third dz1 slot, so that a wave's quarter
+// arrives one tile earlier than its x, and two plane buffers behind the row-table rings: 76 KB, two workgroups per CU.
+template <int MAXNT, int SLOTS, bool SIX>
+struct Dw1Ring {
+    static constexpr int kSlots = SLOTS, kTabRing = 2 * SLOTS;
+    static constexpr bool kShareable = dw1_shares_planes(MAXNT, SLOTS, SIX);
+    static constexpr int kXSlot = d2_xslot(MAXNT), kLds = d2_lds_slots(MAXNT, SLOTS) + (kShareable ? kD2DzSlot : 0);
+    const Dw1Args& a;
+    int wave, lane;
+    bool shared;
+    long long rows, n_it;
+    float* xs;          // this wave's x slots
+    float* dzs;         // the workgroup's dz1 slots
+    int* tabs;          // this wave's ring of row-table slots
+    float* planes;      // (shared planes) the two plane buffers
 
-    auto row0_of = [&](long long m) {       // first launch row of this workgroup's m-th tile; past the end: the last tile
-        if (m >= n_it) m = n_it - 1;        // again (loaded into a slot nobody reads, keeps every group the same size)
+    __device__ __forceinline__ Dw1Ring(const Dw1Args& a_, float* lds, int wave_) : a(a_), wave(wave_) {
+        lane = threadIdx.x & 63;
+        shared = kShareable && !(a.flags & 16384);
+        rows = a.rs.rows;
+        const long long ntiles = (rows + kD2Rows - 1) / kD2Rows;
+        n_it = blockIdx.x < ntiles ? (ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
+        xs = lds + wave * kSlots * kXSlot;
+        dzs = lds + 4 * kSlots * kXSlot;
+        tabs = reinterpret_cast<int*>(lds + kLds) + wave * kTabRing * 64;
+        planes = lds + kLds + 4 * kTabRing * 64;
+    }
+    // first launch row of this workgroup's m-th tile; past the end: the last tile again (loaded into a slot nobody reads,
+    // keeps every group the same size)
+    __device__ __forceinline__ long long row0_of(long long m) const {
+        if (m >= n_it) m = n_it - 1;
         return (blockIdx.x + m * gridDim.x) * kD2Rows;
-    };
+    }
     // lane roles in a load: x -- row 8 g + (lane >> 3) of the tile, 16-byte piece lane & 7 of a k tile;
     // dz1 -- row 4 wave + (lane >> 4), piece lane & 15
-    // The sampler's row table takes the same road, kD2Slots - 1 tiles further ahead: 16 entries per tile into a ring of
+    // The sampler's row table takes the same road, kSlots - 1 tiles further ahead: 16 entries per tile into a ring of
     // 256-byte LDS slots (lanes >= 16 repeat entry 15), read back with two ds_read_b32 per lane when the tile is issued.
+    __device__ __forceinline__ void issue_table(long long t) const {
+        prim::load_lds4(a.rs.srow + row0_of(t) + (lane < 15 ? lane : 15), tabs + (int)(t % kTabRing) * 64);
+    }
+    // this wave's quarter of tile md's dz1 into dz1 slot dslot
+    __device__ __forceinline__ void issue_dz(long long md, int dslot) const {
+        long long r = row0_of(md) + 4 * wave + (lane >> 4);
+        if (r >= rows) r = rows - 1;                // (counts as zero in the product)
+        prim::load_lds16s(a.dz1 + r * 64 + 4 * (lane & 15), dzs + dslot * kD2DzSlot + wave * 256);
+    }
+    // (shared planes) this lane's share of tile t, whose dz1 sits in slot dslot: feature `lane` of rows 4 wave .. + 3, and
+    // where its planes go: the half (wave & 1) of piece (feature tile lane >> 5, lane (lane & 31, g = wave >> 1))
+    __device__ __forceinline__ Dw1Share share_of(long long t, int dslot) const {
+        const long long live = rows - (blockIdx.x + t * gridDim.x) * kD2Rows - 4 * wave;
+        Dw1Share sh;
+        sh.src = dzs + dslot * kD2DzSlot + wave * 256 + lane;
+        sh.dst = planes + (int)(t & 1) * kD2PlaneBuf + (lane >> 5) * 256 + 4 * (32 * (wave >> 1) + (lane & 31)) + 2 * (wave & 1);
+        sh.live = live > 4 ? 4 : live < 0 ? 0 : (int)live;
+        return sh;
+    }
+    // before the first tile, the same for every wave: the row tables of the first tiles; (shared planes) tile 0's share,
+    // the only one no MFMA hides
+    __device__ __forceinline__ void start() const {
+        for (int t = 0; t < kSlots - 1; ++t) issue_table(t);
+        if (shared) issue_dz(0, 0);
+        prim::wait_lds_loads<0>();
+        if (shared) {
+            const Dw1Share sh = share_of(0, 0);
+            dw1_tile_steps6<0, kShareable>(nullptr, nullptr, 0, 0, nullptr, nullptr, &sh);
+        }
+    }
+};
+
+// the tile loop of a wave that owns NT (0 .. MAXNT) k tiles: tiles wave, wave + 4, wave + 8 (, wave + 12) of the slab
+template <int NT, int MAXNT, int SLOTS, bool SIX = false>
+__device__ __forceinline__ void dw1_direct_body(const Dw1Ring<MAXNT, SLOTS, SIX>& ring, int k0) {
+    typedef Dw1Ring<MAXNT, SLOTS, SIX> Ring;
+    constexpr int kD2Slots = SLOTS, kD2TabRing = Ring::kTabRing, kD2XSlot = Ring::kXSlot;
+    constexpr bool SHAREABLE = Ring::kShareable;
+    const Dw1Args& a = ring.a;
+    const bool shared = ring.shared;
+    const int wave = ring.wave, lane = ring.lane, c = lane & 31, h = lane >> 5;
+    const int din = a.rs.din;
+    const long long rows = ring.rows, n_it = ring.n_it;
+    float* xs = ring.xs;
+    float* dzs = ring.dzs;
+    constexpr int G = 2 * NT + 2;                           // loads per group
     const int q8 = lane >> 3;
-    int* tabs = reinterpret_cast<int*>(lds + kD2Lds) + wave * kD2TabRing * 64;
-    auto issue_table = [&](long long t) {
-        prim::load_lds4(a.rs.srow + row0_of(t) + (lane < 15 ? lane : 15), tabs + (int)(t % kD2TabRing) * 64);
-    };
-    auto issue = [&](long long m) {         // loads of tile m into slot m % kD2Slots + the table of tile m + kD2Slots - 1
+    // loads of tile m into slot m % kD2Slots (dz1: of tile md into dz1 slot dslot) + the table of tile m + kD2Slots - 1
+    auto issue = [&](long long m, long long md, int dslot) {
         const int slot = (int)(m % kD2Slots);
         float* xslot = xs + slot * kD2XSlot;
-        const int* tb = tabs + (int)(m % kD2TabRing) * 64;
+        const int* tb = ring.tabs + (int)(m % kD2TabRing) * 64;
         const int sr0 = tb[q8], sr1 = tb[8 + q8];
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
@@ -2799,10 +2922,8 @@ __device__ __forceinline__ void dw1_direct_body(const Dw1Args& a, float* lds, in
             prim::load_lds16s(a.rs.src + (long long)sr0 * din + k, xslot + i * (kD2Rows * 32));
             prim::load_lds16s(a.rs.src + (long long)sr1 * din + k, xslot + i * (kD2Rows * 32) + 256);
         }
-        long long r = row0_of(m) + 4 * wave + (lane >> 4);
-        if (r >= rows) r = rows - 1;                // (zeroed in LDS before the product)
-        prim::load_lds16s(a.dz1 + r * 64 + 4 * (lane & 15), dzs + slot * kD2DzSlot + wave * 256);
-        issue_table(m + kD2Slots - 1);
+        ring.issue_dz(md, dslot);
+        ring.issue_table(m + kD2Slots - 1);
     };
     constexpr int NA = NT > 0 ? NT : 1;
     f32x16 acc[NA][2];
@@ -2812,27 +2933,35 @@ __device__ __forceinline__ void dw1_direct_body(const Dw1Args& a, float* lds, in
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int v = 0; v < 16; ++v) acc[i][t][v] = 0.f;
-    if (n_it == 0) return;
-    for (int t = 0; t < kD2Slots - 1; ++t) issue_table(t);
-    prim::wait_lds_loads<0>();
-    for (int m = 0; m < kD2Slots - 1; ++m) issue(m);
-    const bool stamp = a.dbg != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0;
+    // (shared planes: the dz1 quarter runs one tile ahead of x, through three slots)
+    for (int m = 0; m < kD2Slots - 1; ++m) issue(m, m + shared, m + shared);
+    int dq = 1;                     // (shared planes) the dz1 slot of tile m + 1: (m + 1) % 3
+    const bool stamp = a.dbg != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0;
     for (long long m = 0; m < n_it; ++m) {
         if (stamp && m < 40) a.dbg[512 + 4 * m] = prim::clock();
         // this wave's loads of tile m (and the table of tile m + kD2Slots - 1) have landed: all but the youngest groups
         prim::wait_lds_loads<(kD2Slots - 2) * G>();
         if (stamp && m < 40) a.dbg[512 + 4 * m + 1] = prim::clock();
         const long long live = rows - (blockIdx.x + m * gridDim.x) * kD2Rows;
-        if (live < kD2Rows && 4 * wave + (lane >> 4) >= live)      // last tile: rows past the end of the launch count as zero
+        if (!shared && live < kD2Rows && 4 * wave + (lane >> 4) >= live)      // last tile: rows past the end of the launch count as zero
             *reinterpret_cast<v4*>(dzs + (int)(m % kD2Slots) * kD2DzSlot + wave * 256 + 4 * lane) = v4{0.f, 0.f, 0.f, 0.f};
         __syncthreads();            // ... and everybody else's; all waves are done with tile m - 1's slot
         if (stamp && m < 40) a.dbg[512 + 4 * m + 2] = prim::clock();
-        issue(m + kD2Slots - 1);
+        const int dn = dq == 2 ? 0 : dq + 1;
+        issue(m + kD2Slots - 1, m + kD2Slots - 1 + shared, shared ? dn : (int)((m + kD2Slots - 1) % kD2Slots));
         if (stamp && m < 40) a.dbg[512 + 4 * m + 3] = prim::clock();
         const float* xt = xs + (int)(m % kD2Slots) * kD2XSlot;
         const float* dzt = dzs + (int)(m % kD2Slots) * kD2DzSlot;
-        if (SIX) dw1_tile_steps6<NT>(xt, dzt, c, h, acc);
-        else dw1_tile_steps<NT>(xt, dzt, c, h, acc);
+        if (SHAREABLE) {
+            // (with option bit 16384 the share is still split -- it sits in the same block as the MFMAs -- and nobody reads it)
+            const Dw1Share sh = ring.share_of(m + 1, dq);
+            dw1_tile_steps6<NT, SHAREABLE>(xt, dzt, c, h, acc, shared ? ring.planes + (int)(m & 1) * kD2PlaneBuf : nullptr, &sh);
+            dq = dn;
+        } else if (SIX) {
+            dw1_tile_steps6<NT>(xt, dzt, c, h, acc);
+        } else {
+            dw1_tile_steps<NT>(xt, dzt, c, h, acc);
+        }
     }
     prim::wait_lds_loads<0>();      // (the groups issued past the end)
     float* prow = a.partials + (long long)blockIdx.x * 64 * din;
@@ -2861,11 +2990,14 @@ __global__ void __launch_bounds__(kThreads) mlp_dw1_direct_kernel(Dw1Args a) {
     const int kw = (din - k0 < slab ? ((din - k0 + 31) / 32) * 32 : slab);
     const int ntk = kw / 32;
     const int n_own = (wave < ntk) + (wave + 4 < ntk) + (wave + 8 < ntk) + (MAXNT > 3 && wave + 12 < ntk);
-    if (MAXNT > 3 && n_own == 4) dw1_direct_body<MAXNT, MAXNT, SLOTS, SIX>(a, lds, wave, k0);
-    else if (n_own == 3) dw1_direct_body<3, MAXNT, SLOTS, SIX>(a, lds, wave, k0);
-    else if (n_own == 2) dw1_direct_body<2, MAXNT, SLOTS, SIX>(a, lds, wave, k0);
-    else if (n_own == 1) dw1_direct_body<1, MAXNT, SLOTS, SIX>(a, lds, wave, k0);
-    else dw1_direct_body<0, MAXNT, SLOTS, SIX>(a, lds, wave, k0);
+    const Dw1Ring<MAXNT, SLOTS, SIX> ring(a, lds, wave);
+    if (ring.n_it == 0) return;
+    ring.start();
+    if (MAXNT > 3 && n_own == 4) dw1_direct_body<MAXNT, MAXNT, SLOTS, SIX>(ring, k0);
+    else if (n_own == 3) dw1_direct_body<3, MAXNT, SLOTS, SIX>(ring, k0);
+    else if (n_own == 2) dw1_direct_body<2, MAXNT, SLOTS, SIX>(ring, k0);
+    else if (n_own == 1) dw1_direct_body<1, MAXNT, SLOTS, SIX>(ring, k0);
+    else dw1_direct_body<0, MAXNT, SLOTS, SIX>(ring, k0);
 }
 
 // ---- narrow inputs (din <= 192, din % 4 == 0): up to six k tiles do not split evenly among four waves (five tiles: one wave
@@ -3179,7 +3311,7 @@ inline int& grid_cap_override() {
     return cap;
 }
 // option bits of mappo_mlp_set_flags that exist (tuning / tests only; arithmetic is the per-call `arith` field)
-constexpr int kTuningBits = 1 | 2 | 4 | 8 | 32 | 128 | 256;
+constexpr int kTuningBits = 1 | 2 | 4 | 8 | 32 | 128 | 256 | 16384;
 inline int& tuning_flags_ref() {
     static int v = -1;
     if (v < 0) {
@@ -3354,6 +3486,7 @@ inline int backward(const mappo_mlp_t* m, hipStream_t stream) {
     d.dbg = debug_buffer();
     d.rs = b.rs;
     d.dz1 = m->dz1;
+    d.flags = tuning_flags();
     const long long rt = r_total(L, out);
     float* raw = m->workspace + (long long)kBwdGridCap * rt;        // reduced raw sums of the version-2 chain
     d.partials = m->workspace + chain_floats(L, out);
@@ -3398,7 +3531,7 @@ inline int backward(const mappo_mlp_t* m, hipStream_t stream) {
                              (size_t)(d2_lds(3) + 4 * kD2TabRing * 64) * 4, stream, d);
             } else {
                 MAPPO_LAUNCH((mlp_dw1_direct_kernel<3, 2, true>), dim3((unsigned)gx, (unsigned)gy), kThreads,
-                             (size_t)(d2_lds_slots(3, 2) + 4 * 4 * 64) * 4, stream, d);
+                             (size_t)(d2_lds_slots(3, 2) + kD2DzSlot + 4 * 4 * 64 + 2 * kD2PlaneBuf) * 4, stream, d);
             }
         } else if (maxnt == 4) {
             gx = capped(ceil_div(m->rows, kD2Rows), kD2GridCap / gy > 0 ? kD2GridCap / gy : 1);
