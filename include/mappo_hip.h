@@ -844,6 +844,28 @@ int mappo_simple_speaker_listener_step(double* pos, double* vel, double* landmar
                                        float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
                                        int world_length, int auto_reset, mappo_stream_t stream);
 
+/* ---------------------------------------------------------- K11 family: simple_push worlds on the device ----
+ * One env step of `n_worlds` keep-away worlds (reference onpolicy/envs/mpe/scenarios/simple_push.py:41-104,
+ * environment.py:115-255, core.py:160-190 and :290-321 contact forces; A = num_agents in 2..MAPPO_ENV_MAX_ENTITIES,
+ * L = num_landmarks in 1..2) as one launch.  Agent 0 is the adversary, agents 1..A-1 are good; all move, are silent and
+ * collide softly below distance 0.1 (coincident agents exert no force).  State is updated in place: pos / vel [n, A, 2]
+ * and landmarks [n, L, 2] float64, t [n] int64, goal [n] int64 (the goal landmark all agents share, 0..L-1).  actions
+ * [n, A] int64 in 0..4.  Worlds whose t reaches world_length report done and (auto_reset) restart from fresh_pos
+ * [n, A, 2], 0.8 * fresh_landmarks [n, L, 2] (uniform(-1, 1) draws) and fresh_goal [n], at rest.  Outputs: obs
+ * [n, Da + (A - 1) Dg] float32, one row per world that is also the centralised observation: columns 0:Da the
+ * adversary's observation (velocity, landmarks and other agents relative to it; Da = 2 + 2 L + 2 (A - 1)), then Dg =
+ * 7 + 5 L + 2 (A - 1) columns per good agent in agent order (velocity, the goal relative to it, its colour, landmarks
+ * relative to it, the landmarks' colours, other agents relative to it).  obs is written after a restart, so a restarted
+ * world reports its fresh state; rewards, dones and per_agent are those of the step that ended the episode.  The world
+ * is not collaborative: rewards [n, A, 1] float32 and per_agent [n, A] float64 (the individual_reward info) both hold
+ * each agent's own reward, -|pos - goal| for a good agent and min over good agents |pos_g - goal| - |pos - goal| for the
+ * adversary; dones [n, A] bytes.  MAPPO_E_SHAPE for A < 2 or L outside 1..2, MAPPO_E_TOO_MANY for A > 16. */
+int mappo_simple_push_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,
+                           const int64_t* actions, const double* fresh_pos, const double* fresh_landmarks,
+                           const int64_t* fresh_goal, float* obs, float* rewards, uint8_t* dones, double* per_agent,
+                           int64_t n_worlds, int num_agents, int num_landmarks, int world_length, int auto_reset,
+                           mappo_stream_t stream);
+
 /* ------------------------------------------------------------------- K16: Hanabi tables on the device ----
  * The batched Hanabi stepper of include/hanabi_batch.h (libhanabi_batch.so, host) with its tables in device memory: the
  * same rules, deal and encoder source (csrc/hanabi_rules.h), so for equal seeds and moves every row, reward, status and

@@ -75,6 +75,33 @@ __device__ __forceinline__ void action_force(long long mv, double& fx, double& f
     fy = (mv == 3 ? 1.0 : mv == 4 ? -1.0 : 0.0) * kSens;
 }
 
+// soft contacts between agents that collide below `dist_min`, the sum of their radii (core.py:296-314
+// get_collision_force: softmax penetration, force along the line between the two), added to the force on each agent
+template <int MA>
+__device__ __forceinline__ void add_contact_forces(int A, double dist_min, const double (&px)[MA],
+                                                   const double (&py)[MA], double (&fx)[MA], double (&fy)[MA]) {
+#pragma unroll
+    for (int i = 0; i < MA; ++i) {
+        if (i >= A) continue;
+        double sx = 0.0, sy = 0.0;
+#pragma unroll
+        for (int j = 0; j < MA; ++j) {
+            if (j >= A || j == i) continue;
+            const double dx = px[i] - px[j], dy = py[i] - py[j];
+            const double dist = sqrt(dx * dx + dy * dy);
+            const double x = -(dist - dist_min) / kMargin;
+            const double pen = (fmax(x, 0.0) + log1p(exp(-fabs(x)))) * kMargin;     // logaddexp(0, x) * margin
+            double gx = kForce * dx / dist * pen, gy = kForce * dy / dist * pen;
+            if (!isfinite(gx)) gx = 0.0;                                             // coincident agents: no force
+            if (!isfinite(gy)) gy = 0.0;
+            sx += gx;
+            sy += gy;
+        }
+        fx[i] += sx;
+        fy[i] += sy;
+    }
+}
+
 // core.py:160-175: damping, then force * dt, then the position; no mass / max speed in these scenarios.  Agents before
 // `first` are not movable (core.py:162) and keep their position and velocity
 template <int MA>
@@ -90,16 +117,17 @@ __device__ __forceinline__ void integrate(int A, double (&px)[MA], double (&py)[
     }
 }
 
-// individual rewards, the shared reward and the done flag of a world whose clock now shows t; -> the world restarts
+// individual rewards, the reward each agent is paid and the done flag of a world whose clock now shows t; -> the world
+// restarts.  A collaborative world (environment.py:141-143 shared_reward) pays every agent `total`, any other its own
 template <int MA>
 __device__ __forceinline__ bool write_outcome(const World& s, long long w, int A, long long t, const double (&pa)[MA],
-                                              double total) {
+                                              double total, bool shared = true) {
     const bool done = t >= s.world_length;
 #pragma unroll
     for (int i = 0; i < MA; ++i) {
         if (i >= A) continue;
         s.per_agent[w * A + i] = pa[i];
-        s.rew[w * A + i] = (float)total;
+        s.rew[w * A + i] = (float)(shared ? total : pa[i]);
         s.done[w * A + i] = done ? 1 : 0;
     }
     return done && s.auto_reset;
@@ -157,26 +185,7 @@ __global__ void __launch_bounds__(64) spread_step_kernel(Args a) {
     for (int i = 0; i < kMax; ++i) {
         if (i < A) action_force(a.act[w * A + i], fx[i], fy[i]);
     }
-#pragma unroll
-    for (int i = 0; i < kMax; ++i) {
-        if (i >= A) continue;
-        double sx = 0.0, sy = 0.0;
-#pragma unroll
-        for (int j = 0; j < kMax; ++j) {
-            if (j >= A || j == i) continue;
-            const double dx = px[i] - px[j], dy = py[i] - py[j];
-            const double dist = sqrt(dx * dx + dy * dy);
-            const double x = -(dist - 2 * kSize) / kMargin;
-            const double pen = (fmax(x, 0.0) + log1p(exp(-fabs(x)))) * kMargin;     // logaddexp(0, x) * margin
-            double gx = kForce * dx / dist * pen, gy = kForce * dy / dist * pen;
-            if (!isfinite(gx)) gx = 0.0;                                             // coincident agents: no force
-            if (!isfinite(gy)) gy = 0.0;
-            sx += gx;
-            sy += gy;
-        }
-        fx[i] += sx;
-        fy[i] += sy;
-    }
+    add_contact_forces(A, 2 * kSize, px, py, fx, fy);
     integrate(A, px, py, vx, vy, fx, fy);
     long long t = s.t[w] + 1;
     // ---- reward (simple_spread.py:60-84): -sum over landmarks of the closest agent's distance, -1 per contact
@@ -387,6 +396,108 @@ __global__ void __launch_bounds__(64) speaker_listener_step_kernel(SpeakerArgs a
     for (int sym = 0; sym < kSpkSymbols; ++sym) o[k++] = comm == sym ? 1.f : 0.f;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// simple_push (keep-away; scenarios/simple_push.py): agent 0, the adversary, has to keep the good agents 1..A-1 away from
+// the goal landmark all of them share; every agent moves, is silent and collides (radius 0.05).  Not collaborative: each
+// agent is paid its own reward.  One goal per world, advanced in place like simple_speaker_listener's; the observation
+// leaves as ONE row per world, adversary's columns first, then the good agents' in agent order.
+constexpr int kPushLandmarks = 2;           // the landmark palette has a channel for two (simple_push.py:43-45)
+constexpr double kPushSize = 0.05, kPushLandmarkScale = 0.8;
+
+struct PushArgs {
+    World s;                        // s.obs: [N, (2 + 2 L + 2 (A - 1)) + (A - 1) (7 + 5 L + 2 (A - 1))]
+    long long* goal;                // [N] goal landmark, 0..L-1
+    const long long* act;           // [N, A] action indices 0..4
+    const long long* fresh_goal;    // [N] 0..L-1
+    int A, L;
+};
+
+__global__ void __launch_bounds__(64) push_step_kernel(PushArgs a) {
+    const long long w = (long long)blockIdx.x * 64 + threadIdx.x;
+    const World& s = a.s;
+    if (w >= s.n) return;
+    const int A = a.A, L = a.L;
+    constexpr int ML = kPushLandmarks;
+    double px[kMax], py[kMax], vx[kMax], vy[kMax], lx[ML] = {0.0, 0.0}, ly[ML] = {0.0, 0.0};
+    load_world(s, w, A, L, px, py, vx, vy, lx, ly);
+    long long goal = a.goal[w];
+    // ---- forces: action + soft contacts
+    double fx[kMax], fy[kMax];
+#pragma unroll
+    for (int i = 0; i < kMax; ++i) {
+        if (i < A) action_force(a.act[w * A + i], fx[i], fy[i]);
+    }
+    add_contact_forces(A, 2 * kPushSize, px, py, fx, fy);
+    integrate(A, px, py, vx, vy, fx, fy);
+    long long t = s.t[w] + 1;
+    // ---- reward (simple_push.py:66-82): a good agent -|pos - goal|, the adversary the closest good agent's distance to
+    // the goal minus its own
+    {
+        const double gx = goal == 0 ? lx[0] : lx[1], gy = goal == 0 ? ly[0] : ly[1];
+        double pa[kMax];
+        double own = 0.0, nearest = 1e300;
+#pragma unroll
+        for (int i = 0; i < kMax; ++i) {
+            if (i >= A) continue;
+            const double dx = px[i] - gx, dy = py[i] - gy;
+            const double d = sqrt(dx * dx + dy * dy);
+            pa[i] = -d;
+            if (i == 0) own = d; else nearest = fmin(nearest, d);
+        }
+        pa[0] = nearest - own;
+        const bool restart = write_outcome(s, w, A, t, pa, 0.0, false);
+        if (restart) {
+            t = 0;
+            restart_from_fresh(s, w, A, L, kPushLandmarkScale, px, py, vx, vy, lx, ly);
+            goal = a.fresh_goal[w];
+            a.goal[w] = goal;
+        }
+        store_world(s, w, A, L, t, restart, px, py, vx, vy, lx, ly);
+    }
+    // ---- observation of the (possibly restarted) world (simple_push.py:84-104).  Adversary: own velocity, landmarks and
+    // other agents relative to it.  Good agent: own velocity, the goal relative to it, own colour (0.75 on the goal's
+    // channel), landmarks relative to it, the landmarks' colours (0.9 on a landmark's own channel), other agents
+    const double gx = goal == 0 ? lx[0] : lx[1], gy = goal == 0 ? ly[0] : ly[1];
+    const int Da = 2 + 2 * L + 2 * (A - 1), Dg = 7 + 5 * L + 2 * (A - 1);
+    float* row = s.obs + w * (Da + (long long)(A - 1) * Dg);
+#pragma unroll
+    for (int i = 0; i < kMax; ++i) {
+        if (i >= A) continue;
+        float* o = i == 0 ? row : row + Da + (i - 1) * Dg;
+        int k = 0;
+        o[k++] = (float)vx[i];
+        o[k++] = (float)vy[i];
+        if (i > 0) {
+            o[k++] = (float)(gx - px[i]);
+            o[k++] = (float)(gy - py[i]);
+            o[k++] = 0.25f;
+            o[k++] = goal == 0 ? 0.75f : 0.25f;
+            o[k++] = goal == 1 ? 0.75f : 0.25f;
+        }
+#pragma unroll
+        for (int l = 0; l < ML; ++l) {
+            if (l >= L) continue;
+            o[k++] = (float)(lx[l] - px[i]);
+            o[k++] = (float)(ly[l] - py[i]);
+        }
+        if (i > 0) {
+#pragma unroll
+            for (int l = 0; l < ML; ++l) {
+                if (l >= L) continue;
+                o[k++] = 0.1f;
+                o[k++] = l == 0 ? 0.9f : 0.1f;
+                o[k++] = l == 1 ? 0.9f : 0.1f;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kMax; ++j) {
+            if (j >= A || j == i) continue;
+            o[k++] = (float)(px[j] - px[i]);
+            o[k++] = (float)(py[j] - py[i]);
+        }
+    }
+}
+
 // one thread per world, 64 to a block
 template <typename ArgsT>
 int launch_step(void (*kernel)(ArgsT), const ArgsT& a, mappo_stream_t stream_) {
@@ -441,4 +552,21 @@ extern "C" int mappo_simple_speaker_listener_step(double* pos, double* vel, doub
                   n_worlds, world_length, auto_reset};
     return launch_step(speaker_listener_step_kernel,
                        SpeakerArgs{s, i64(goal), i64(comm), i64(actions), i64(fresh_goal)}, stream_);
+}
+
+extern "C" int mappo_simple_push_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,
+                                      const int64_t* actions, const double* fresh_pos, const double* fresh_landmarks,
+                                      const int64_t* fresh_goal, float* obs, float* rewards, uint8_t* dones,
+                                      double* per_agent, int64_t n_worlds, int num_agents, int num_landmarks,
+                                      int world_length, int auto_reset, mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !goal || !actions || !obs || !rewards || !dones || !per_agent)
+        return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks || !fresh_goal)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || num_agents < 2 || num_landmarks < 1 || num_landmarks > kPushLandmarks || world_length < 1)
+        return MAPPO_E_SHAPE;
+    if (num_agents > kMax) return MAPPO_E_TOO_MANY;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    return launch_step(push_step_kernel, PushArgs{s, i64(goal), i64(actions), i64(fresh_goal), num_agents, num_landmarks},
+                       stream_);
 }

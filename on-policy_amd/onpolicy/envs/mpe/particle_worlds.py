@@ -1,7 +1,7 @@
 """What the multi-agent particle scenarios share: the physics constants (reference onpolicy/envs/mpe/core.py), the lazy
 ``infos`` of the device-resident envs, and ``TorchParticleWorlds``, the base class of worlds held as tensors on the
 policy's device.  A scenario (simple_spread.py, simple_reference.py,
-simple_speaker_listener.py) adds its spaces, its extra state, its forces, reward and observation, and the one native call
+simple_speaker_listener.py, simple_push.py) adds its spaces, its extra state, its forces, reward and observation, and the one native call
 that is its step on a HIP device.
 """
 DT = 0.1
@@ -52,8 +52,10 @@ class TorchParticleWorlds(object):
     A scenario supplies ``_fresh``, ``_forces``, ``_reward``, ``_obs``, ``_kernel_actions`` and ``_launch``; one with
     state of its own extends ``state_names`` and ``_restart``.  One whose agents observe vectors of different widths
     passes the widths as a tuple for ``obs_dim`` (kept per agent in ``obs_dims``) and overrides ``_obs_shape``;
-    one with agents that do not move sets ``_movable``."""
+    one with agents that do not move sets ``_movable``; one that is not collaborative (environment.py:49-50, :140-143) clears
+    ``shared_reward`` and pays every agent its own reward instead of the agents' sum."""
     device_resident = True
+    shared_reward = True        # every agent is paid the sum of the agents' rewards (world.collaborative)
     # the tensors a captured rollout graph snapshots / restores and expects to stay in place (runner/shared/rollout_graph.py)
     state_names = ("pos", "vel", "landmarks", "t")
     landmark_scale = 1.0        # restarted landmarks lie at landmark_scale * U(-1, 1)
@@ -104,6 +106,18 @@ class TorchParticleWorlds(object):
         self.vel = torch.where(w, torch.zeros_like(self.vel), self.vel)
         self.landmarks = torch.where(w, self.landmark_scale * fresh[1], self.landmarks)
         self.t = torch.where(which, torch.zeros_like(self.t), self.t)
+
+    def _contact_forces(self, dist_min):
+        """Soft contacts between agents closer than ``dist_min``, the sum of their radii (core.py:290-321) -> the force
+        on each agent [N, A, 2].  Coincident agents exert none (the reference divides by zero there).  Needs
+        ``self._others``, the [A, A] mask without its diagonal."""
+        torch = self._torch
+        delta = self.pos[:, :, None, :] - self.pos[:, None, :, :]
+        dist = torch.sqrt((delta ** 2).sum(-1))
+        pen = torch.logaddexp(torch.zeros_like(dist), -(dist - dist_min) / CONTACT_MARGIN) * CONTACT_MARGIN
+        f = CONTACT_FORCE * delta / dist[..., None] * pen[..., None]
+        f = torch.where(self._others[None, :, :, None], f, torch.zeros_like(f))       # no self force (0 / 0 there)
+        return torch.nan_to_num(f, nan=0.0, posinf=0.0, neginf=0.0).sum(2)
 
     def reset(self):
         self._restart(self._torch.ones(self.n, dtype=self._torch.bool, device=self.device), self._fresh())
@@ -160,7 +174,10 @@ class TorchParticleWorlds(object):
         self.vel, self.pos = vel, pos
         self.t = self.t + 1
         per_agent = self._reward()
-        rewards = per_agent.sum(-1, keepdim=True).expand(self.n, self.a).unsqueeze(-1).to(torch.float32)
+        if self.shared_reward:
+            rewards = per_agent.sum(-1, keepdim=True).expand(self.n, self.a).unsqueeze(-1).to(torch.float32)
+        else:
+            rewards = per_agent[..., None].to(torch.float32)
         done_env = self.t >= self.world_length
         dones = done_env[:, None].expand(self.n, self.a)
         if self.auto_reset:

@@ -131,13 +131,7 @@ class TorchSimpleSpread(TorchParticleWorlds):
         return torch.cat([self.vel, self.pos, rel_land, rel_other, comm], -1).to(torch.float32)
 
     def _collision_forces(self):
-        torch = self._torch
-        delta = self.pos[:, :, None, :] - self.pos[:, None, :, :]
-        dist = torch.sqrt((delta ** 2).sum(-1))
-        pen = torch.logaddexp(torch.zeros_like(dist), -(dist - 2 * AGENT_SIZE) / CONTACT_MARGIN) * CONTACT_MARGIN
-        f = CONTACT_FORCE * delta / dist[..., None] * pen[..., None]
-        f = torch.where(self._others[None, :, :, None], f, torch.zeros_like(f))       # no self force (0 / 0 there)
-        return torch.nan_to_num(f, nan=0.0, posinf=0.0, neginf=0.0).sum(2)
+        return self._contact_forces(2 * AGENT_SIZE)
 
     def _reward(self):
         torch = self._torch

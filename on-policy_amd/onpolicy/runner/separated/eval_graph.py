@@ -1,7 +1,7 @@
 """One evaluation step of the separated runner's device-resident eval loop as ONE graph launch: the separated analogue
 of runner/shared/eval_graph.py, which it inherits everything from but the shape of the carried state.
 
-With one policy per agent (``--share_policy``: simple_speaker_listener) an evaluation step (reference
+With one policy per agent (``--share_policy``: simple_speaker_listener, simple_push) an evaluation step (reference
 onpolicy/runner/separated/mpe_runner.py:179-235) is every agent's actor forward and deterministic action (K14 mode), the
 agents' integer actions side by side into the env step, and masks / RNN states per agent.  The carried state is kept per
 agent -- current observation (``eval_envs.agent_obs(obs, i)``), masks, the actor's RNN states -- next to the one totals

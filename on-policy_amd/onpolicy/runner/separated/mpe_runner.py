@@ -6,7 +6,7 @@ As in the shared runner only the integer actions (device -> host) and the new ob
 dones (host -> device) cross the PCIe bus per step; each agent's values, log-probs and RNN states go
 from its policy straight into its HBM buffer.
 
-With the worlds on the device (``envs.device_resident``: envs/mpe/simple_speaker_listener.py) nothing crosses it:
+With the worlds on the device (``envs.device_resident``: envs/mpe/simple_speaker_listener.py, simple_push.py) nothing crosses it:
 ``warmup`` / ``collect`` / ``insert`` work on tensors -- the env takes the policies' integer actions side by side and
 hands back one observation row per world, of which ``envs.agent_obs(obs, i)`` is agent i's view and the row itself the
 centralised critics' input -- and ``run`` replays the whole step from one captured graph where

@@ -3,7 +3,7 @@ runner/shared/rollout_graph.py, whose warm-up, capture, snapshot / restore of wo
 check and fall-back to the eager loop it inherits.
 
 With one policy and one buffer per agent (``--share_policy``: simple_speaker_listener, whose agents differ in their
-observation and action spaces) a rollout step is every agent's actor and critic forward and action sampling (K14), the
+observation and action spaces, and simple_push, whose two or more agents differ in their observations and rewards) a rollout step is every agent's actor and critic forward and action sampling (K14), the
 agents' integer actions side by side into the env step (K11 family), and the mask / RNN-state bookkeeping per agent
 (reference onpolicy/runner/separated/mpe_runner.py:94-177: collect -> envs.step -> insert): twice the launches of the
 shared step on half the rows.  The captured step reads and advances a carried state per agent -- current observation,

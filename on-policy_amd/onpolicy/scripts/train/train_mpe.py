@@ -7,10 +7,12 @@ Differences: simple_spread comes from the in-tree vectorised implementation (no 
 ``--use_device_env`` keeps the training worlds on the GPU next to policy and buffer); with ``--use_device_env``
 simple_reference comes from the in-tree device implementation as well (envs/mpe/simple_reference.py, shared-policy
 runner only), and so does simple_speaker_listener (envs/mpe/simple_speaker_listener.py: two agents with different
-spaces, so the separated runner only -- ``--share_policy`` -- with rmappo / mappo / ippo); every other case --
-simple_reference or simple_speaker_listener without the flag, any other scenario, and the eval envs of ``--use_eval``
+spaces, so the separated runner only -- ``--share_policy`` -- with rmappo / mappo / ippo) and simple_push
+(envs/mpe/simple_push.py: one adversary and num_agents - 1 good agents with different observations and rewards of their
+own, 1 or 2 landmarks; the separated runner only, like simple_speaker_listener); every other case -- simple_reference,
+simple_speaker_listener or simple_push without the flag, any other scenario, and the eval envs of ``--use_eval``
 in every case but one -- is built per worker from an external env tree (MAPPO_ENVS_PATH).  The exception:
-``--use_device_eval`` (with ``--use_eval --use_device_env``, rmappo / mappo / ippo) builds the eval worlds of the three
+``--use_device_eval`` (with ``--use_eval --use_device_env``, rmappo / mappo / ippo) builds the eval worlds of the four
 device scenarios in-tree on the device too, and ``eval()`` then runs on tensors, its step as one captured graph launch
 (runner/shared/eval_graph.py).  wandb / setproctitle are optional.
 Example (BASELINE.json configs[0]):
@@ -26,11 +28,16 @@ The reference's train_mpe_comm.sh on the device (``--share_policy`` is a store_f
         --scenario_name simple_speaker_listener --num_agents 2 --num_landmarks 3 --n_rollout_threads 128 \
         --num_mini_batch 1 --episode_length 25 --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 \
         --critic_lr 7e-4 --share_policy --use_device_env
+Keep-away on the device (an episode is 25 steps whatever --episode_length says, as in the reference):
+    python -m onpolicy.scripts.train.train_mpe --env_name MPE --algorithm_name rmappo --scenario_name simple_push \
+        --num_agents 2 --num_landmarks 2 --n_rollout_threads 128 --num_mini_batch 1 --episode_length 25 \
+        --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 --critic_lr 7e-4 --share_policy --use_device_env
 """
 import argparse
 import sys
 
 from onpolicy.config import get_config
+from onpolicy.envs.mpe.simple_push import TorchSimplePush
 from onpolicy.envs.mpe.simple_reference import TorchSimpleReference
 from onpolicy.envs.mpe.simple_speaker_listener import TorchSimpleSpeakerListener
 from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread, VecSimpleSpread
@@ -39,9 +46,9 @@ from onpolicy.scripts.train import _launch
 
 # scenarios with an in-tree device implementation (--use_device_env; row f1): the worlds are held on the policy's device
 DEVICE_ENVS = {"simple_spread": TorchSimpleSpread, "simple_reference": TorchSimpleReference,
-               "simple_speaker_listener": TorchSimpleSpeakerListener}
+               "simple_speaker_listener": TorchSimpleSpeakerListener, "simple_push": TorchSimplePush}
 # ... of which these run under the separated runner (one policy per agent: the agents' spaces differ), the rest under the shared
-SEPARATED_DEVICE_ENVS = ("simple_speaker_listener",)
+SEPARATED_DEVICE_ENVS = ("simple_speaker_listener", "simple_push")
 
 
 def make_train_env(all_args, n_threads=None, seed_offset=0, device=None):
@@ -73,9 +80,9 @@ def parse_args(args, parser):
     parser.add_argument("--num_landmarks", type=int, default=3)
     parser.add_argument('--num_agents', type=int, default=2, help="number of players")
     parser.add_argument('--use_device_env', action='store_true', default=False,
-                        help="simple_spread or simple_reference (shared-policy runner) or simple_speaker_listener "
-                             "(separated runner) with the training worlds held as tensors on the policy's device: "
-                             "no per-step host round trip")
+                        help="simple_spread or simple_reference (shared-policy runner) or simple_speaker_listener or "
+                             "simple_push (separated runner: --share_policy) with the training worlds held as "
+                             "tensors on the policy's device: no per-step host round trip")
     # (argparse.SUPPRESS: the attribute exists only when the flag is given, so a default parse carries the reference's flags
     # and --use_device_env, nothing else; readers use getattr(args, "fused_multi_loss", False))
     parser.add_argument('--fused_multi_loss', action='store_true', default=argparse.SUPPRESS,
@@ -111,6 +118,10 @@ def main(args):
                 "--use_device_env: %s with the shared-policy runner, %s with the separated runner (rmappo / mappo / ippo) "
                 "only" % (" / ".join(k for k in DEVICE_ENVS if k not in SEPARATED_DEVICE_ENVS),
                           " / ".join(SEPARATED_DEVICE_ENVS)))
+        if scenario == "simple_push" and all_args.num_landmarks not in (1, 2):
+            raise NotImplementedError("--use_device_env: simple_push colours landmark l on channel l + 1 of three, so "
+                                      "--num_landmarks is 1 or 2 (the reference fails at 3), not %d"
+                                      % all_args.num_landmarks)
     envs = make_train_env(all_args, device=device if all_args.use_device_env else None)
     eval_envs = make_train_env(all_args, all_args.n_eval_rollout_threads, 50000,
                                device=device if device_eval else None) if all_args.use_eval else None

@@ -1,11 +1,13 @@
 #!/usr/bin/env python
 """One 25-step rollout of the reference's train_mpe_comm.sh (MPE simple_speaker_listener, 2 agents, 3 landmarks, rmappo,
-128 rollout threads, hidden 64, one policy per agent) on one MI355X with the worlds on the device (--use_device_env),
+128 rollout threads, hidden 64, one policy per agent) -- or, with ``--scenario simple_push --num_agents A --num_landmarks
+L``, of keep-away at the same script family's shape -- on one MI355X with the worlds on the device (--use_device_env),
 timed two ways in the same process, alternating: the separated runner's eager device loop (collect -> envs.step ->
 insert: what MAPPO_ROLLOUT_GRAPH=0 runs) and the captured step (runner/separated/rollout_graph.py: one graph launch + one
 slab write per agent).  Both start every rollout from the buffers' row 0 and leave the same fields behind.
 
-    python tools/speaker_listener_rollout.py [--reps 30] [--warmup 5] [--commit HASH] [--out file.json]
+    python tools/speaker_listener_rollout.py [--reps 30] [--warmup 5] [--commit HASH] [--out file.json [--append]]
+    python tools/speaker_listener_rollout.py --scenario simple_push --num_agents 3 --num_landmarks 2 ...
 
 Per way: median, quartiles, 10th / 90th percentile and range of the rollout's wall time (host clock around work that ends
 in a device synchronise) over ``--reps`` rollouts after ``--warmup`` untimed ones.  ``spread_ms`` is the larger of the two
@@ -35,6 +37,9 @@ def summary(ms):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scenario", default="simple_speaker_listener", choices=("simple_speaker_listener", "simple_push"))
+    ap.add_argument("--num_agents", type=int, default=2)
+    ap.add_argument("--num_landmarks", type=int, default=None, help="default: 3 for simple_speaker_listener, 2 for simple_push")
     ap.add_argument("--threads", type=int, default=128)
     ap.add_argument("--episode_length", type=int, default=25)
     ap.add_argument("--hidden_size", type=int, default=64)
@@ -43,7 +48,9 @@ if __name__ == "__main__":
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--commit", default=None, help="commit the measurement was made on (recorded in the JSON line)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--append", action="store_true", help="add the JSON line to --out (one line per shape) instead of replacing it")
     opt = ap.parse_args()
+    landmarks = opt.num_landmarks if opt.num_landmarks is not None else (2 if opt.scenario == "simple_push" else 3)
     os.environ.setdefault("MAPPO_RESULTS_DIR", tempfile.mkdtemp())
     os.environ["MAPPO_ROLLOUT_GRAPH"] = "1"
     import torch
@@ -51,7 +58,8 @@ if __name__ == "__main__":
     assert torch.cuda.is_available(), "a timing needs the GPU"
     T, N = opt.episode_length, opt.threads
     argv = ["--env_name", "MPE", "--algorithm_name", opt.algorithm_name, "--experiment_name", "check",
-            "--scenario_name", "simple_speaker_listener", "--num_agents", "2", "--num_landmarks", "3", "--seed", "1",
+            "--scenario_name", opt.scenario, "--num_agents", str(opt.num_agents), "--num_landmarks", str(landmarks),
+            "--seed", "1",
             "--n_training_threads", "1", "--n_rollout_threads", str(N), "--num_mini_batch", "1",
             "--episode_length", str(T), "--num_env_steps", str(T * N), "--ppo_epoch", "15", "--gain", "0.01",
             "--lr", "7e-4", "--critic_lr", "7e-4", "--share_policy", "--hidden_size", str(opt.hidden_size), "--use_wandb",
@@ -96,9 +104,10 @@ if __name__ == "__main__":
     launches, activities, why = None, None, None
     spread = max(e["p90_ms"] - e["p10_ms"], g["p90_ms"] - g["p10_ms"])
 
-    out = {"config": "train_mpe_comm.sh: MPE simple_speaker_listener, 2 agents, 3 landmarks, %s, n_rollout_threads=%d, "
+    out = {"config": "%s: MPE %s, %d agents, %d landmarks, %s, n_rollout_threads=%d, "
                      "episode_length=%d, hidden_size=%d, one policy per agent, 1 x MI355X, worlds on the device"
-                     % (opt.algorithm_name, N, T, opt.hidden_size),
+                     % ("train_mpe_comm.sh" if opt.scenario == "simple_speaker_listener" else "train_mpe.sh family",
+                        opt.scenario, opt.num_agents, landmarks, opt.algorithm_name, N, T, opt.hidden_size),
            "commit": opt.commit, "what": "wall time of one %d-step rollout, %d alternating repetitions after %d warm-up "
                                          "rollouts each" % (T, opt.reps, opt.warmup),
            "eager": e, "graph": g, "spread_ms": round(spread, 4),
@@ -111,11 +120,13 @@ if __name__ == "__main__":
            "graph_launches_per_step": "1 graph launch + %d slab writes (+ the integer actions' conversion per agent)"
                                       % len(runner.buffer)}
 
+    kept = open(opt.out).read() if opt.out and opt.append and os.path.exists(opt.out) else ""
+
     def write():
         if opt.out:
             os.makedirs(os.path.dirname(os.path.abspath(opt.out)), exist_ok=True)
             with open(opt.out, "w") as f:
-                f.write(json.dumps(out) + "\n")
+                f.write(kept + json.dumps(out) + "\n")
     write()                                 # (the timings are on disk before the profiler starts)
     try:                                    # in a run of its own: tracing slows the host
         from torch.profiler import ProfilerActivity, profile
