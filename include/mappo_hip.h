@@ -866,6 +866,33 @@ int mappo_simple_push_step(double* pos, double* vel, double* landmarks, int64_t*
                            int64_t n_worlds, int num_agents, int num_landmarks, int world_length, int auto_reset,
                            mappo_stream_t stream);
 
+/* ----------------------------------------------------------- K11 family: simple_tag worlds on the device ----
+ * One env step of `n_worlds` predator-prey worlds (reference onpolicy/envs/mpe/scenarios/simple_tag.py:6-144,
+ * environment.py:115-255, core.py:207-321: action force, integration with a top speed, contact forces; A = num_agents in
+ * 2..MAPPO_ENV_MAX_ENTITIES, Nadv = num_adversaries in 1..A-1, L = num_landmarks in 1..MAPPO_TAG_MAX_LANDMARKS) as one
+ * launch.  Agents 0..Nadv-1 are adversaries (radius 0.075, acceleration 3, top speed 1.0), the G = A - Nadv agents after
+ * them are good (0.05, 4, 1.3); all move, are silent and collide softly with each other below the sum of their radii and
+ * with the landmarks (radius 0.2, immovable: the agent alone takes the force) below radius + 0.2; coincident centres
+ * exert no force.  The action force is acceleration^2 times the direction, 9 or 16 (the reference applies the
+ * acceleration as the action's sensitivity and as the force's factor); after damping and force the speed is clamped to
+ * the top speed.  State is updated in place: pos / vel [n, A, 2] and landmarks [n, L, 2] float64, t [n] int64.  actions
+ * [n, A] int64 in 0..4.  Worlds whose t reaches world_length report done and (auto_reset) restart from fresh_pos
+ * [n, A, 2] and 0.8 * fresh_landmarks [n, L, 2] (uniform(-1, 1) draws), at rest.  Outputs: obs [n, Nadv Da + G Dg]
+ * float32, one row per world that is also the centralised observation, the agents' columns in agent order: velocity,
+ * position, landmarks relative to the agent, other agents relative to it, the velocities of the other good agents
+ * (Da = 4 + 2 L + 2 (A - 1) + 2 G for an adversary, Dg = Da - 2 for a good agent).  obs is written after a restart, so a
+ * restarted world reports its fresh state; rewards, dones and per_agent are those of the step that ended the episode.
+ * The world is not collaborative: rewards [n, A, 1] float32 and per_agent [n, A] float64 (the individual_reward info)
+ * both hold each agent's own reward.  With hits the number of (good agent, adversary) pairs closer than 0.125, every
+ * adversary is paid 10 hits; a good agent -10 per adversary closer to it than 0.125, minus bound(|x|) + bound(|y|) with
+ * bound(x) = 0 below 0.9, 10 (x - 0.9) below 1.0 and min(exp(2 x - 2), 10) from there on; dones [n, A] bytes.
+ * MAPPO_E_SHAPE for Nadv outside 1..A-1 or L < 1, MAPPO_E_TOO_MANY for A > 16 or L > 4. */
+#define MAPPO_TAG_MAX_LANDMARKS 4
+int mappo_simple_tag_step(double* pos, double* vel, double* landmarks, int64_t* t, const int64_t* actions,
+                          const double* fresh_pos, const double* fresh_landmarks, float* obs, float* rewards,
+                          uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents, int num_adversaries,
+                          int num_landmarks, int world_length, int auto_reset, mappo_stream_t stream);
+
 /* ------------------------------------------------------------------- K16: Hanabi tables on the device ----
  * The batched Hanabi stepper of include/hanabi_batch.h (libhanabi_batch.so, host) with its tables in device memory: the
  * same rules, deal and encoder source (csrc/hanabi_rules.h), so for equal seeds and moves every row, reward, status and

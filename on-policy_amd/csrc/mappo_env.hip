@@ -69,16 +69,37 @@ __device__ __forceinline__ void load_world(const World& s, long long w, int A, i
     load_xy(s.land, w, L, lx, ly);
 }
 
-// movement index -> force (environment.py: u[0] += a[1] - a[2], u[1] += a[3] - a[4], x sensitivity)
-__device__ __forceinline__ void action_force(long long mv, double& fx, double& fy) {
-    fx = (mv == 1 ? 1.0 : mv == 2 ? -1.0 : 0.0) * kSens;
-    fy = (mv == 3 ? 1.0 : mv == 4 ? -1.0 : 0.0) * kSens;
+// movement index -> force (environment.py: u[0] += a[1] - a[2], u[1] += a[3] - a[4], x sensitivity; an agent with an
+// acceleration of its own is scaled by that instead)
+__device__ __forceinline__ void action_force(long long mv, double& fx, double& fy, double scale = kSens) {
+    fx = (mv == 1 ? 1.0 : mv == 2 ? -1.0 : 0.0) * scale;
+    fy = (mv == 3 ? 1.0 : mv == 4 ? -1.0 : 0.0) * scale;
 }
 
-// soft contacts between agents that collide below `dist_min`, the sum of their radii (core.py:296-314
-// get_collision_force: softmax penetration, force along the line between the two), added to the force on each agent
+// a property that the adversaries (agents before `n_adv`) and the good agents of a scenario hold different values of.
+// A scenario whose agents are all alike passes n_adv = 0 as a literal, and the choice folds away
+struct ByKind {
+    int n_adv;
+    double adversary, good;
+    __device__ __forceinline__ double of(int i) const { return i < n_adv ? adversary : good; }
+};
+
+// the force of one soft contact on the entity at distance (dx, dy) from the other, which collide below `dist_min`, the
+// sum of their radii (core.py:296-314 get_collision_force: softmax penetration, force along the line between the two)
+__device__ __forceinline__ void contact_force(double dx, double dy, double dist_min, double& sx, double& sy) {
+    const double dist = sqrt(dx * dx + dy * dy);
+    const double x = -(dist - dist_min) / kMargin;
+    const double pen = (fmax(x, 0.0) + log1p(exp(-fabs(x)))) * kMargin;     // logaddexp(0, x) * margin
+    double gx = kForce * dx / dist * pen, gy = kForce * dy / dist * pen;
+    if (!isfinite(gx)) gx = 0.0;                                             // coincident centres: no force
+    if (!isfinite(gy)) gy = 0.0;
+    sx += gx;
+    sy += gy;
+}
+
+// soft contacts between agents of radius `size`, added to the force on each agent
 template <int MA>
-__device__ __forceinline__ void add_contact_forces(int A, double dist_min, const double (&px)[MA],
+__device__ __forceinline__ void add_contact_forces(int A, const ByKind& size, const double (&px)[MA],
                                                    const double (&py)[MA], double (&fx)[MA], double (&fy)[MA]) {
 #pragma unroll
     for (int i = 0; i < MA; ++i) {
@@ -87,31 +108,53 @@ __device__ __forceinline__ void add_contact_forces(int A, double dist_min, const
 #pragma unroll
         for (int j = 0; j < MA; ++j) {
             if (j >= A || j == i) continue;
-            const double dx = px[i] - px[j], dy = py[i] - py[j];
-            const double dist = sqrt(dx * dx + dy * dy);
-            const double x = -(dist - dist_min) / kMargin;
-            const double pen = (fmax(x, 0.0) + log1p(exp(-fabs(x)))) * kMargin;     // logaddexp(0, x) * margin
-            double gx = kForce * dx / dist * pen, gy = kForce * dy / dist * pen;
-            if (!isfinite(gx)) gx = 0.0;                                             // coincident agents: no force
-            if (!isfinite(gy)) gy = 0.0;
-            sx += gx;
-            sy += gy;
+            contact_force(px[i] - px[j], py[i] - py[j], size.of(i) + size.of(j), sx, sy);
         }
         fx[i] += sx;
         fy[i] += sy;
     }
 }
 
-// core.py:160-175: damping, then force * dt, then the position; no mass / max speed in these scenarios.  Agents before
-// `first` are not movable (core.py:162) and keep their position and velocity
-template <int MA>
+// soft contacts of the agents with landmarks of radius `land_size` that collide and never move (core.py:318-320): the
+// agent alone takes the force, away from the landmark
+template <int MA, int ML>
+__device__ __forceinline__ void add_landmark_contact_forces(int A, int L, const ByKind& size, double land_size,
+                                                            const double (&px)[MA], const double (&py)[MA],
+                                                            const double (&lx)[ML], const double (&ly)[ML],
+                                                            double (&fx)[MA], double (&fy)[MA]) {
+#pragma unroll
+    for (int i = 0; i < MA; ++i) {
+        if (i >= A) continue;
+        double sx = 0.0, sy = 0.0;
+#pragma unroll
+        for (int l = 0; l < ML; ++l) {
+            if (l >= L) continue;
+            contact_force(px[i] - lx[l], py[i] - ly[l], size.of(i) + land_size, sx, sy);
+        }
+        fx[i] += sx;
+        fy[i] += sy;
+    }
+}
+
+// core.py:265-278: damping, then force * dt (every mass is 1), then -- kClamp, for scenarios whose agents have one -- the
+// top speed `max_speed`, then the position.  Agents before `first` are not movable (core.py:267) and keep their position
+// and velocity
+template <bool kClamp = false, int MA>
 __device__ __forceinline__ void integrate(int A, double (&px)[MA], double (&py)[MA], double (&vx)[MA], double (&vy)[MA],
-                                          const double (&fx)[MA], const double (&fy)[MA], int first = 0) {
+                                          const double (&fx)[MA], const double (&fy)[MA], int first = 0,
+                                          const ByKind& max_speed = ByKind{0, 0.0, 0.0}) {
 #pragma unroll
     for (int i = 0; i < MA; ++i) {
         if (i < first || i >= A) continue;
         vx[i] = vx[i] * (1 - kDamping) + fx[i] * kDt;
         vy[i] = vy[i] * (1 - kDamping) + fy[i] * kDt;
+        if (kClamp) {
+            const double speed = sqrt(vx[i] * vx[i] + vy[i] * vy[i]), top = max_speed.of(i);
+            if (speed > top) {
+                vx[i] = vx[i] / speed * top;
+                vy[i] = vy[i] / speed * top;
+            }
+        }
         px[i] = px[i] + vx[i] * kDt;
         py[i] = py[i] + vy[i] * kDt;
     }
@@ -185,7 +228,7 @@ __global__ void __launch_bounds__(64) spread_step_kernel(Args a) {
     for (int i = 0; i < kMax; ++i) {
         if (i < A) action_force(a.act[w * A + i], fx[i], fy[i]);
     }
-    add_contact_forces(A, 2 * kSize, px, py, fx, fy);
+    add_contact_forces(A, ByKind{0, kSize, kSize}, px, py, fx, fy);
     integrate(A, px, py, vx, vy, fx, fy);
     long long t = s.t[w] + 1;
     // ---- reward (simple_spread.py:60-84): -sum over landmarks of the closest agent's distance, -1 per contact
@@ -427,7 +470,7 @@ __global__ void __launch_bounds__(64) push_step_kernel(PushArgs a) {
     for (int i = 0; i < kMax; ++i) {
         if (i < A) action_force(a.act[w * A + i], fx[i], fy[i]);
     }
-    add_contact_forces(A, 2 * kPushSize, px, py, fx, fy);
+    add_contact_forces(A, ByKind{0, kPushSize, kPushSize}, px, py, fx, fy);
     integrate(A, px, py, vx, vy, fx, fy);
     long long t = s.t[w] + 1;
     // ---- reward (simple_push.py:66-82): a good agent -|pos - goal|, the adversary the closest good agent's distance to
@@ -494,6 +537,114 @@ __global__ void __launch_bounds__(64) push_step_kernel(PushArgs a) {
             if (j >= A || j == i) continue;
             o[k++] = (float)(px[j] - px[i]);
             o[k++] = (float)(py[j] - py[i]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// simple_tag (predator-prey; scenarios/simple_tag.py): agents 0..Nadv-1, the adversaries, chase the good agents Nadv..A-1
+// among landmarks that collide and never move.  An adversary is large and slow, a good agent small and fast; every agent
+// moves, is silent, collides and has a top speed.  Not collaborative: each agent is paid its own reward.  No state besides
+// the particle state; the observation leaves as ONE row per world, the agents' columns in agent order.
+constexpr int kTagLandmarks = MAPPO_TAG_MAX_LANDMARKS;
+constexpr double kTagLandmarkScale = 0.8, kTagLandmarkSize = 0.2, kTagCatch = 10.0;
+// (adversary, good agent)
+constexpr double kTagSize[2] = {0.075, 0.05}, kTagAccel[2] = {3.0, 4.0}, kTagMaxSpeed[2] = {1.0, 1.3};
+
+struct TagArgs {
+    World s;                        // s.obs: [N, Nadv (4 + 2 L + 2 (A - 1) + 2 G) + G (4 + 2 L + 2 (A - 1) + 2 (G - 1))], G = A - Nadv
+    const long long* act;           // [N, A] action indices 0..4
+    int A, n_adv, L;
+};
+
+// the penalty for leaving the screen along one axis (simple_tag.py:100-105), x = |coordinate|
+__device__ __forceinline__ double tag_bound(double x) {
+    return x < 0.9 ? 0.0 : x < 1.0 ? (x - 0.9) * 10 : fmin(exp(2 * x - 2), 10.0);
+}
+
+__global__ void __launch_bounds__(64) tag_step_kernel(TagArgs a) {
+    const long long w = (long long)blockIdx.x * 64 + threadIdx.x;
+    const World& s = a.s;
+    if (w >= s.n) return;
+    const int A = a.A, L = a.L, n_adv = a.n_adv;
+    constexpr int ML = kTagLandmarks;
+    double px[kMax], py[kMax], vx[kMax], vy[kMax], lx[ML], ly[ML];
+    load_world(s, w, A, L, px, py, vx, vy, lx, ly);
+    const ByKind size{n_adv, kTagSize[0], kTagSize[1]};
+    // ---- forces: action (the acceleration acts twice: as the action's sensitivity, environment.py:233-236, and as the
+    // force's factor, core.py:236-237) + soft contacts with agents and landmarks
+    {
+        const ByKind scale{n_adv, kTagAccel[0] * kTagAccel[0], kTagAccel[1] * kTagAccel[1]};
+        double fx[kMax], fy[kMax];
+#pragma unroll
+        for (int i = 0; i < kMax; ++i) {
+            if (i < A) action_force(a.act[w * A + i], fx[i], fy[i], scale.of(i));
+        }
+        add_contact_forces(A, size, px, py, fx, fy);
+        add_landmark_contact_forces(A, L, size, kTagLandmarkSize, px, py, lx, ly, fx, fy);
+        integrate<true>(A, px, py, vx, vy, fx, fy, 0, ByKind{n_adv, kTagMaxSpeed[0], kTagMaxSpeed[1]});
+    }
+    long long t = s.t[w] + 1;
+    // ---- reward (simple_tag.py:86-126): a good agent -10 per adversary that touches it and the penalty for leaving the
+    // screen, every adversary +10 per (good agent, adversary) pair in touch, whoever the adversary
+    {
+        double pa[kMax];
+        int hits = 0;
+#pragma unroll
+        for (int g = 0; g < kMax; ++g) {
+            if (g < n_adv || g >= A) continue;
+            int mine = 0;
+#pragma unroll
+            for (int j = 0; j < kMax; ++j) {
+                if (j >= n_adv || j >= A) continue;
+                const double dx = px[g] - px[j], dy = py[g] - py[j];
+                mine += sqrt(dx * dx + dy * dy) < kTagSize[1] + kTagSize[0];
+            }
+            hits += mine;
+            pa[g] = -kTagCatch * mine - (tag_bound(fabs(px[g])) + tag_bound(fabs(py[g])));
+        }
+#pragma unroll
+        for (int i = 0; i < kMax; ++i) {
+            if (i < n_adv) pa[i] = kTagCatch * hits;
+        }
+        const bool restart = write_outcome(s, w, A, t, pa, 0.0, false);
+        if (restart) {
+            t = 0;
+            restart_from_fresh(s, w, A, L, kTagLandmarkScale, px, py, vx, vy, lx, ly);
+        }
+        store_world(s, w, A, L, t, restart, px, py, vx, vy, lx, ly);
+    }
+    // ---- observation of the (possibly restarted) world (simple_tag.py:128-144): own velocity, own position, landmarks
+    // and other agents relative to the agent, the velocities of the other good agents
+    const int G = A - n_adv;
+    const int Da = 4 + 2 * L + 2 * (A - 1) + 2 * G, Dg = Da - 2;
+    float* row = s.obs + w * ((long long)n_adv * Da + (long long)G * Dg);
+#pragma unroll
+    for (int i = 0; i < kMax; ++i) {
+        if (i >= A) continue;
+        float* o = i < n_adv ? row + i * Da : row + n_adv * Da + (i - n_adv) * Dg;
+        int k = 0;
+        o[k++] = (float)vx[i];
+        o[k++] = (float)vy[i];
+        o[k++] = (float)px[i];
+        o[k++] = (float)py[i];
+#pragma unroll
+        for (int l = 0; l < ML; ++l) {
+            if (l >= L) continue;
+            o[k++] = (float)(lx[l] - px[i]);
+            o[k++] = (float)(ly[l] - py[i]);
+        }
+#pragma unroll
+        for (int j = 0; j < kMax; ++j) {
+            if (j >= A || j == i) continue;
+            o[k++] = (float)(px[j] - px[i]);
+            o[k++] = (float)(py[j] - py[i]);
+        }
+#pragma unroll
+        for (int j = 0; j < kMax; ++j) {
+            if (j < n_adv || j >= A || j == i) continue;
+            o[k++] = (float)vx[j];
+            o[k++] = (float)vy[j];
         }
     }
 }
@@ -569,4 +720,19 @@ extern "C" int mappo_simple_push_step(double* pos, double* vel, double* landmark
                   n_worlds, world_length, auto_reset};
     return launch_step(push_step_kernel, PushArgs{s, i64(goal), i64(actions), i64(fresh_goal), num_agents, num_landmarks},
                        stream_);
+}
+
+extern "C" int mappo_simple_tag_step(double* pos, double* vel, double* landmarks, int64_t* t, const int64_t* actions,
+                                     const double* fresh_pos, const double* fresh_landmarks, float* obs, float* rewards,
+                                     uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents,
+                                     int num_adversaries, int num_landmarks, int world_length, int auto_reset,
+                                     mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !actions || !obs || !rewards || !dones || !per_agent) return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || num_adversaries < 1 || num_adversaries >= num_agents || num_landmarks < 1 || world_length < 1)
+        return MAPPO_E_SHAPE;
+    if (num_agents > kMax || num_landmarks > kTagLandmarks) return MAPPO_E_TOO_MANY;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    return launch_step(tag_step_kernel, TagArgs{s, i64(actions), num_agents, num_adversaries, num_landmarks}, stream_);
 }

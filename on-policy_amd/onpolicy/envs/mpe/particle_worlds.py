@@ -1,7 +1,7 @@
 """What the multi-agent particle scenarios share: the physics constants (reference onpolicy/envs/mpe/core.py), the lazy
 ``infos`` of the device-resident envs, and ``TorchParticleWorlds``, the base class of worlds held as tensors on the
 policy's device.  A scenario (simple_spread.py, simple_reference.py,
-simple_speaker_listener.py, simple_push.py) adds its spaces, its extra state, its forces, reward and observation, and the one native call
+simple_speaker_listener.py, simple_push.py, simple_tag.py) adds its spaces, its extra state, its forces, reward and observation, and the one native call
 that is its step on a HIP device.
 """
 DT = 0.1
@@ -53,16 +53,19 @@ class TorchParticleWorlds(object):
     state of its own extends ``state_names`` and ``_restart``.  One whose agents observe vectors of different widths
     passes the widths as a tuple for ``obs_dim`` (kept per agent in ``obs_dims``) and overrides ``_obs_shape``;
     one with agents that do not move sets ``_movable``; one that is not collaborative (environment.py:49-50, :140-143) clears
-    ``shared_reward`` and pays every agent its own reward instead of the agents' sum."""
+    ``shared_reward`` and pays every agent its own reward instead of the agents' sum; one whose agents differ in
+    acceleration passes ``action_scale`` per agent, and one whose agents have a top speed (core.py:272-277) sets
+    ``_max_speed``."""
     device_resident = True
     shared_reward = True        # every agent is paid the sum of the agents' rewards (world.collaborative)
     # the tensors a captured rollout graph snapshots / restores and expects to stay in place (runner/shared/rollout_graph.py)
     state_names = ("pos", "vel", "landmarks", "t")
     landmark_scale = 1.0        # restarted landmarks lie at landmark_scale * U(-1, 1)
     _movable = None             # bool [1, A, 1] where some agents are not integrated (core.py:162); None: all move
+    _max_speed = None           # float64 [1, A, 1], each agent's top speed (core.py:272-277); None: no clamp
 
     def __init__(self, n_threads, num_agents, num_landmarks, episode_length, seed, auto_reset, device, obs_dim,
-                 action_space):
+                 action_space, action_scale=SENSITIVITY):
         import torch
         self._torch = torch
         self.auto_reset = auto_reset      # finished worlds restart inside step(), as the vec-env workers do
@@ -86,7 +89,13 @@ class TorchParticleWorlds(object):
         self.landmarks = torch.zeros(self.n, self.l, 2, **f64)
         self.t = torch.zeros(self.n, dtype=torch.int64, device=self.device)
         # action index -> force direction (environment.py: u[0] += a[1] - a[2], u[1] += a[3] - a[4])
-        self._directions = torch.tensor([[0, 0], [1, 0], [-1, 0], [0, 1], [0, -1]], **f64) * SENSITIVITY
+        # times the action scale: the sensitivity, or one scale per agent ([A, 5, 2] then, see ``_action_forces``)
+        self._directions = torch.tensor([[0, 0], [1, 0], [-1, 0], [0, 1], [0, -1]], **f64)
+        if isinstance(action_scale, (tuple, list)):
+            assert len(action_scale) == self.a, action_scale
+            self._directions = torch.tensor(action_scale, **f64).view(self.a, 1, 1) * self._directions
+        else:
+            self._directions = self._directions * action_scale
 
     def _uniform(self, *shape):
         torch = self._torch
@@ -107,16 +116,31 @@ class TorchParticleWorlds(object):
         self.landmarks = torch.where(w, self.landmark_scale * fresh[1], self.landmarks)
         self.t = torch.where(which, torch.zeros_like(self.t), self.t)
 
+    def _action_forces(self, idx):
+        """Movement indices [N, A] -> the action force on each agent [N, A, 2] where the action scale is per agent."""
+        return self._directions[self._torch.arange(self.a, device=self.device), idx]
+
     def _contact_forces(self, dist_min):
-        """Soft contacts between agents closer than ``dist_min``, the sum of their radii (core.py:290-321) -> the force
-        on each agent [N, A, 2].  Coincident agents exert none (the reference divides by zero there).  Needs
-        ``self._others``, the [A, A] mask without its diagonal."""
+        """Soft contacts between agents closer than ``dist_min``, the sum of their radii (core.py:290-321; a scalar, or
+        [A, A] where the radii differ) -> the force on each agent [N, A, 2].  Coincident agents exert none (the
+        reference divides by zero there).  Needs ``self._others``, the [A, A] mask without its diagonal."""
         torch = self._torch
         delta = self.pos[:, :, None, :] - self.pos[:, None, :, :]
         dist = torch.sqrt((delta ** 2).sum(-1))
         pen = torch.logaddexp(torch.zeros_like(dist), -(dist - dist_min) / CONTACT_MARGIN) * CONTACT_MARGIN
         f = CONTACT_FORCE * delta / dist[..., None] * pen[..., None]
         f = torch.where(self._others[None, :, :, None], f, torch.zeros_like(f))       # no self force (0 / 0 there)
+        return torch.nan_to_num(f, nan=0.0, posinf=0.0, neginf=0.0).sum(2)
+
+    def _landmark_contact_forces(self, dist_min):
+        """Soft contacts between agents and landmarks that collide and do not move (core.py:318-320): ``dist_min`` is the
+        sum of the two radii, a scalar or [A, 1] per agent -> the force on each agent [N, A, 2], away from the landmark.
+        An agent on a landmark's centre takes none, as with coincident agents."""
+        torch = self._torch
+        delta = self.pos[:, :, None, :] - self.landmarks[:, None, :, :]
+        dist = torch.sqrt((delta ** 2).sum(-1))
+        pen = torch.logaddexp(torch.zeros_like(dist), -(dist - dist_min) / CONTACT_MARGIN) * CONTACT_MARGIN
+        f = CONTACT_FORCE * delta / dist[..., None] * pen[..., None]
         return torch.nan_to_num(f, nan=0.0, posinf=0.0, neginf=0.0).sum(2)
 
     def reset(self):
@@ -166,8 +190,11 @@ class TorchParticleWorlds(object):
     def _step_ops(self, actions):
         torch = self._torch
         force = self._forces(actions)
-        # core.py:160-175: damping, then force * dt; no mass / max speed in these scenarios
+        # core.py:265-278: damping, then force * dt (every mass is 1), then the top speed where agents have one
         vel = self.vel * (1 - DAMPING) + force * DT
+        if self._max_speed is not None:
+            speed = torch.sqrt(vel[..., 0:1] ** 2 + vel[..., 1:2] ** 2)
+            vel = torch.where(speed > self._max_speed, vel / speed * self._max_speed, vel)
         pos = self.pos + vel * DT
         if self._movable is not None:
             vel, pos = torch.where(self._movable, vel, self.vel), torch.where(self._movable, pos, self.pos)

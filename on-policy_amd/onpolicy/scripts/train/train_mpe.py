@@ -9,10 +9,11 @@ simple_reference comes from the in-tree device implementation as well (envs/mpe/
 runner only), and so does simple_speaker_listener (envs/mpe/simple_speaker_listener.py: two agents with different
 spaces, so the separated runner only -- ``--share_policy`` -- with rmappo / mappo / ippo) and simple_push
 (envs/mpe/simple_push.py: one adversary and num_agents - 1 good agents with different observations and rewards of their
-own, 1 or 2 landmarks; the separated runner only, like simple_speaker_listener); every other case -- simple_reference,
-simple_speaker_listener or simple_push without the flag, any other scenario, and the eval envs of ``--use_eval``
-in every case but one -- is built per worker from an external env tree (MAPPO_ENVS_PATH).  The exception:
-``--use_device_eval`` (with ``--use_eval --use_device_env``, rmappo / mappo / ippo) builds the eval worlds of the four
+own, 1 or 2 landmarks; the separated runner only, like simple_speaker_listener) and simple_tag (envs/mpe/simple_tag.py:
+``--num_adversaries`` adversaries followed by ``--num_good_agents`` good agents, num_agents their sum; the separated
+runner only); every other case -- simple_reference, simple_speaker_listener, simple_push or simple_tag without the
+flag, any other scenario, and the eval envs of ``--use_eval`` in every case but one -- is built per worker from an external env tree (MAPPO_ENVS_PATH).  The exception:
+``--use_device_eval`` (with ``--use_eval --use_device_env``, rmappo / mappo / ippo) builds the eval worlds of the
 device scenarios in-tree on the device too, and ``eval()`` then runs on tensors, its step as one captured graph launch
 (runner/shared/eval_graph.py).  wandb / setproctitle are optional.
 Example (BASELINE.json configs[0]):
@@ -32,6 +33,11 @@ Keep-away on the device (an episode is 25 steps whatever --episode_length says, 
     python -m onpolicy.scripts.train.train_mpe --env_name MPE --algorithm_name rmappo --scenario_name simple_push \
         --num_agents 2 --num_landmarks 2 --n_rollout_threads 128 --num_mini_batch 1 --episode_length 25 \
         --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 --critic_lr 7e-4 --share_policy --use_device_env
+Predator-prey on the device, three adversaries against one good agent (25-step episodes as well):
+    python -m onpolicy.scripts.train.train_mpe --env_name MPE --algorithm_name rmappo --scenario_name simple_tag \
+        --num_agents 4 --num_adversaries 3 --num_good_agents 1 --num_landmarks 2 --n_rollout_threads 128 \
+        --num_mini_batch 1 --episode_length 25 --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 \
+        --critic_lr 7e-4 --share_policy --use_device_env
 """
 import argparse
 import sys
@@ -41,23 +47,32 @@ from onpolicy.envs.mpe.simple_push import TorchSimplePush
 from onpolicy.envs.mpe.simple_reference import TorchSimpleReference
 from onpolicy.envs.mpe.simple_speaker_listener import TorchSimpleSpeakerListener
 from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread, VecSimpleSpread
+from onpolicy.envs.mpe.simple_tag import TorchSimpleTag
 from onpolicy.scripts.train import _launch
 
 
 # scenarios with an in-tree device implementation (--use_device_env; row f1): the worlds are held on the policy's device
 DEVICE_ENVS = {"simple_spread": TorchSimpleSpread, "simple_reference": TorchSimpleReference,
-               "simple_speaker_listener": TorchSimpleSpeakerListener, "simple_push": TorchSimplePush}
+               "simple_speaker_listener": TorchSimpleSpeakerListener, "simple_push": TorchSimplePush,
+               "simple_tag": TorchSimpleTag}
 # ... of which these run under the separated runner (one policy per agent: the agents' spaces differ), the rest under the shared
-SEPARATED_DEVICE_ENVS = ("simple_speaker_listener", "simple_push")
+SEPARATED_DEVICE_ENVS = ("simple_speaker_listener", "simple_push", "simple_tag")
+TAG_DEFAULTS = (3, 1)       # adversaries, good agents where --num_adversaries / --num_good_agents are not given
+
+
+def tag_counts(all_args):
+    """-> (adversaries, good agents) of a simple_tag run."""
+    return (getattr(all_args, "num_adversaries", TAG_DEFAULTS[0]), getattr(all_args, "num_good_agents", TAG_DEFAULTS[1]))
 
 
 def make_train_env(all_args, n_threads=None, seed_offset=0, device=None):
     n = all_args.n_rollout_threads if n_threads is None else n_threads
     seed_offset += 1000 * getattr(all_args, "rollout_thread_offset", 0)      # data-parallel rank: its own worlds
     if device is not None and all_args.scenario_name in DEVICE_ENVS:
+        extra = {"num_adversaries": tag_counts(all_args)[0]} if all_args.scenario_name == "simple_tag" else {}
         return DEVICE_ENVS[all_args.scenario_name](n, all_args.num_agents, all_args.num_landmarks,
                                                    all_args.episode_length, seed=all_args.seed + seed_offset,
-                                                   device=device)
+                                                   device=device, **extra)
     if all_args.scenario_name == "simple_spread":       # built in, all worlds advanced by one numpy pass
         return VecSimpleSpread(n, all_args.num_agents, all_args.num_landmarks, all_args.episode_length,
                                seed=all_args.seed + seed_offset)
@@ -80,8 +95,8 @@ def parse_args(args, parser):
     parser.add_argument("--num_landmarks", type=int, default=3)
     parser.add_argument('--num_agents', type=int, default=2, help="number of players")
     parser.add_argument('--use_device_env', action='store_true', default=False,
-                        help="simple_spread or simple_reference (shared-policy runner) or simple_speaker_listener or "
-                             "simple_push (separated runner: --share_policy) with the training worlds held as "
+                        help="simple_spread or simple_reference (shared-policy runner) or simple_speaker_listener, "
+                             "simple_push or simple_tag (separated runner: --share_policy) with the training worlds held as "
                              "tensors on the policy's device: no per-step host round trip")
     # (argparse.SUPPRESS: the attribute exists only when the flag is given, so a default parse carries the reference's flags
     # and --use_device_env, nothing else; readers use getattr(args, "fused_multi_loss", False))
@@ -94,6 +109,12 @@ def parse_args(args, parser):
                              "policy's device like the training worlds, eval() runs on tensors with the deterministic "
                              "action from one kernel launch, and its step is replayed from a captured graph "
                              "(MAPPO_EVAL_GRAPH=0: the eager tensor loop)")
+    # (SUPPRESS as above; the external env tree's simple_tag reads the same two attributes)
+    parser.add_argument('--num_adversaries', type=int, default=argparse.SUPPRESS,
+                        help="simple_tag: agents 0 .. num_adversaries - 1 chase the others (3 where not given)")
+    parser.add_argument('--num_good_agents', type=int, default=argparse.SUPPRESS,
+                        help="simple_tag: the agents that are chased (1 where not given); with --use_device_env "
+                             "num_agents = num_adversaries + num_good_agents")
     return parser.parse_known_args(args)[0]
 
 
@@ -122,6 +143,12 @@ def main(args):
             raise NotImplementedError("--use_device_env: simple_push colours landmark l on channel l + 1 of three, so "
                                       "--num_landmarks is 1 or 2 (the reference fails at 3), not %d"
                                       % all_args.num_landmarks)
+        if scenario == "simple_tag":
+            adv, good = tag_counts(all_args)
+            if adv < 1 or good < 1 or all_args.num_agents != adv + good:
+                raise NotImplementedError("--use_device_env: simple_tag needs num_agents = num_adversaries + "
+                                          "num_good_agents with at least one of each, not %d = %d + %d"
+                                          % (all_args.num_agents, adv, good))
     envs = make_train_env(all_args, device=device if all_args.use_device_env else None)
     eval_envs = make_train_env(all_args, all_args.n_eval_rollout_threads, 50000,
                                device=device if device_eval else None) if all_args.use_eval else None

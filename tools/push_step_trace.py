@@ -1,10 +1,11 @@
 #!/usr/bin/env python
 """Steps device-resident simple_push worlds through their kernel path (``mappo_simple_push_step``, one launch per step)
-and nothing else, for a kernel-trace run of its own:
+-- or, with ``--scenario simple_tag --num_adversaries V``, simple_tag worlds through ``mappo_simple_tag_step`` -- and
+nothing else, for a kernel-trace run of its own:
 
     rocprofv3 --kernel-trace --stats -f csv -d out -o push -- python tools/push_step_trace.py --worlds 4096
 
-The trace's ``push_step_kernel`` row is the step kernel's own time at that number of worlds (the generator draws of a
+The trace's ``push_step_kernel`` (``tag_step_kernel``) row is the step kernel's own time at that number of worlds (the generator draws of a
 step and the action tensor are separate kernels in the same trace).  Prints one JSON line with the shape and the wall
 time per step as the host sees it.
 """
@@ -19,6 +20,8 @@ sys.path.insert(0, os.path.join(ROOT, "on-policy_amd"))
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scenario", default="simple_push", choices=("simple_push", "simple_tag"))
+    ap.add_argument("--num_adversaries", type=int, default=3, help="simple_tag only: of --num_agents")
     ap.add_argument("--worlds", type=int, default=128)
     ap.add_argument("--num_agents", type=int, default=2)
     ap.add_argument("--num_landmarks", type=int, default=2)
@@ -26,9 +29,14 @@ if __name__ == "__main__":
     opt = ap.parse_args()
     import torch
     from onpolicy.envs.mpe.simple_push import TorchSimplePush
+    from onpolicy.envs.mpe.simple_tag import TorchSimpleTag
     assert torch.cuda.is_available(), "a trace needs the GPU"
     dev = torch.device("cuda", 0)
-    env = TorchSimplePush(opt.worlds, opt.num_agents, opt.num_landmarks, seed=1, device=dev)
+    if opt.scenario == "simple_tag":
+        env = TorchSimpleTag(opt.worlds, opt.num_agents, opt.num_landmarks, seed=1, device=dev,
+                             num_adversaries=opt.num_adversaries)
+    else:
+        env = TorchSimplePush(opt.worlds, opt.num_agents, opt.num_landmarks, seed=1, device=dev)
     assert env.graph_safe
     env.reset()
     g = torch.Generator(device=dev).manual_seed(2)
@@ -41,6 +49,6 @@ if __name__ == "__main__":
         env.step(actions[i % 8])
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
-    print(json.dumps({"scenario": "simple_push", "worlds": opt.worlds, "num_agents": opt.num_agents,
+    print(json.dumps({"scenario": opt.scenario, "worlds": opt.worlds, "num_agents": opt.num_agents,
                       "num_landmarks": opt.num_landmarks, "steps": opt.steps,
                       "host_us_per_step": round(1e6 * wall / opt.steps, 2)}))

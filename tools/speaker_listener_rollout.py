@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """One 25-step rollout of the reference's train_mpe_comm.sh (MPE simple_speaker_listener, 2 agents, 3 landmarks, rmappo,
 128 rollout threads, hidden 64, one policy per agent) -- or, with ``--scenario simple_push --num_agents A --num_landmarks
-L``, of keep-away at the same script family's shape -- on one MI355X with the worlds on the device (--use_device_env),
+L``, of keep-away at the same script family's shape, or, with ``--scenario simple_tag --num_adversaries V
+--num_good_agents G --num_landmarks L``, of predator-prey -- on one MI355X with the worlds on the device (--use_device_env),
 timed two ways in the same process, alternating: the separated runner's eager device loop (collect -> envs.step ->
 insert: what MAPPO_ROLLOUT_GRAPH=0 runs) and the captured step (runner/separated/rollout_graph.py: one graph launch + one
 slab write per agent).  Both start every rollout from the buffers' row 0 and leave the same fields behind.
 
     python tools/speaker_listener_rollout.py [--reps 30] [--warmup 5] [--commit HASH] [--out file.json [--append]]
     python tools/speaker_listener_rollout.py --scenario simple_push --num_agents 3 --num_landmarks 2 ...
+    python tools/speaker_listener_rollout.py --scenario simple_tag --num_adversaries 3 --num_good_agents 1 ...
 
 Per way: median, quartiles, 10th / 90th percentile and range of the rollout's wall time (host clock around work that ends
 in a device synchronise) over ``--reps`` rollouts after ``--warmup`` untimed ones.  ``spread_ms`` is the larger of the two
@@ -37,9 +39,11 @@ def summary(ms):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenario", default="simple_speaker_listener", choices=("simple_speaker_listener", "simple_push"))
-    ap.add_argument("--num_agents", type=int, default=2)
-    ap.add_argument("--num_landmarks", type=int, default=None, help="default: 3 for simple_speaker_listener, 2 for simple_push")
+    ap.add_argument("--scenario", default="simple_speaker_listener", choices=("simple_speaker_listener", "simple_push", "simple_tag"))
+    ap.add_argument("--num_agents", type=int, default=2, help="simple_tag: --num_adversaries + --num_good_agents instead")
+    ap.add_argument("--num_adversaries", type=int, default=3, help="simple_tag only")
+    ap.add_argument("--num_good_agents", type=int, default=1, help="simple_tag only")
+    ap.add_argument("--num_landmarks", type=int, default=None, help="default: 3 for simple_speaker_listener, 2 otherwise")
     ap.add_argument("--threads", type=int, default=128)
     ap.add_argument("--episode_length", type=int, default=25)
     ap.add_argument("--hidden_size", type=int, default=64)
@@ -50,7 +54,10 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", action="store_true", help="add the JSON line to --out (one line per shape) instead of replacing it")
     opt = ap.parse_args()
-    landmarks = opt.num_landmarks if opt.num_landmarks is not None else (2 if opt.scenario == "simple_push" else 3)
+    landmarks = opt.num_landmarks if opt.num_landmarks is not None else (3 if opt.scenario == "simple_speaker_listener" else 2)
+    tag = ["--num_adversaries", str(opt.num_adversaries), "--num_good_agents", str(opt.num_good_agents)]
+    if opt.scenario == "simple_tag":
+        opt.num_agents = opt.num_adversaries + opt.num_good_agents
     os.environ.setdefault("MAPPO_RESULTS_DIR", tempfile.mkdtemp())
     os.environ["MAPPO_ROLLOUT_GRAPH"] = "1"
     import torch
@@ -63,7 +70,7 @@ if __name__ == "__main__":
             "--n_training_threads", "1", "--n_rollout_threads", str(N), "--num_mini_batch", "1",
             "--episode_length", str(T), "--num_env_steps", str(T * N), "--ppo_epoch", "15", "--gain", "0.01",
             "--lr", "7e-4", "--critic_lr", "7e-4", "--share_policy", "--hidden_size", str(opt.hidden_size), "--use_wandb",
-            "--log_interval", "1000", "--save_interval", "1000", "--use_device_env"]
+            "--log_interval", "1000", "--save_interval", "1000", "--use_device_env"] + (tag if opt.scenario == "simple_tag" else [])
     runner = train_mpe.main(argv)           # one whole iteration: builds everything, captures the step, one train()
     graph = runner.rollout_graph
     assert graph is not None and graph.graph is not None, "the rollout step was not captured"
@@ -104,10 +111,12 @@ if __name__ == "__main__":
     launches, activities, why = None, None, None
     spread = max(e["p90_ms"] - e["p10_ms"], g["p90_ms"] - g["p10_ms"])
 
-    out = {"config": "%s: MPE %s, %d agents, %d landmarks, %s, n_rollout_threads=%d, "
+    agents = ("%d agents" % opt.num_agents if opt.scenario != "simple_tag" else
+              "%d adversaries against %d good agents" % (opt.num_adversaries, opt.num_good_agents))
+    out = {"config": "%s: MPE %s, %s, %d landmarks, %s, n_rollout_threads=%d, "
                      "episode_length=%d, hidden_size=%d, one policy per agent, 1 x MI355X, worlds on the device"
                      % ("train_mpe_comm.sh" if opt.scenario == "simple_speaker_listener" else "train_mpe.sh family",
-                        opt.scenario, opt.num_agents, landmarks, opt.algorithm_name, N, T, opt.hidden_size),
+                        opt.scenario, agents, landmarks, opt.algorithm_name, N, T, opt.hidden_size),
            "commit": opt.commit, "what": "wall time of one %d-step rollout, %d alternating repetitions after %d warm-up "
                                          "rollouts each" % (T, opt.reps, opt.warmup),
            "eager": e, "graph": g, "spread_ms": round(spread, 4),
