@@ -893,6 +893,38 @@ int mappo_simple_tag_step(double* pos, double* vel, double* landmarks, int64_t* 
                           uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents, int num_adversaries,
                           int num_landmarks, int world_length, int auto_reset, mappo_stream_t stream);
 
+/* ---------------------------------------------------- K11 family: simple_world_comm worlds on the device ----
+ * One env step of `n_worlds` worlds of predator-prey with forests, food and a speaking leader (reference
+ * onpolicy/envs/mpe/scenarios/simple_world_comm.py, environment.py:54-98 and :115-255, core.py:207-321; A = num_agents in
+ * 2..MAPPO_ENV_MAX_ENTITIES, Nadv = num_adversaries in 1..A-1, L = num_landmarks, the obstacles, in
+ * 1..MAPPO_WORLD_COMM_MAX_OBSTACLES) as one launch.  Agents, forces, top speeds and integration are simple_tag's with a
+ * good agent's radius 0.045.  The landmark list holds L obstacles (radius 0.2, the only ones that exert contact forces),
+ * then 2 pieces of food (0.03), then 2 forests (0.3): Lt = L + 4.  Agent 0, the leader, also says a word.  State is
+ * updated in place: pos / vel [n, A, 2] and landmarks [n, Lt, 2] float64, t [n] and comm [n] int64 (the leader's last
+ * word, -1 while nothing has been said since a restart).  actions [n, A + 1] int64: the leader's movement 0..4, its word
+ * 0..3, the other agents' movements.  Worlds whose t reaches world_length report done and (auto_reset) restart from
+ * fresh_pos [n, A, 2] and 0.8 * fresh_landmarks [n, Lt, 2] (uniform(-1, 1) draws), at rest, comm -1.
+ * Agent i is inside forest f when closer to its centre than its radius + 0.3, and sees agent j iff i is the leader, both
+ * are inside forest 0, both are inside forest 1, or neither is inside any forest.  Outputs: obs [n, Nadv Da + G Dg]
+ * float32, one row per world that is also the centralised observation, the agents' columns in agent order.  An
+ * adversary: velocity, position, landmarks relative to the agent, other agents relative to it ((0, 0) for one it does
+ * not see), the good agents' velocities ((0, 0) likewise), inside forest 0 / 1 as +-1, comm as a one-hot of 4
+ * (Da = 4 + 2 Lt + 2 (A - 1) + 2 G + 6).  A good agent: velocity, position, landmarks, other agents (masked), the two
+ * forest flags, the other good agents' velocities (masked) (Dg = 4 + 2 Lt + 2 (A - 1) + 2 + 2 (G - 1)).  obs is written
+ * after a restart, so a restarted world reports its fresh state; rewards, dones and per_agent are those of the step that
+ * ended the episode.  The world is not collaborative: rewards [n, A, 1] float32 and per_agent [n, A] float64 both hold
+ * each agent's own reward.  With hits the number of (good agent, adversary) pairs closer than 0.12, adversary a is paid
+ * 5 hits - 0.1 x its distance to the nearest good agent; a good agent -5 per adversary closer to it than 0.12,
+ * -2 (bound(|x|) + bound(|y|)) with simple_tag's bound, +2 per food closer than 0.075 and +0.05 x its distance to the
+ * nearest food; dones [n, A] bytes.  MAPPO_E_SHAPE for Nadv outside 1..A-1 or L < 1, MAPPO_E_TOO_MANY for A > 16 or
+ * L > 4. */
+#define MAPPO_WORLD_COMM_MAX_OBSTACLES 4
+int mappo_simple_world_comm_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* comm,
+                                 const int64_t* actions, const double* fresh_pos, const double* fresh_landmarks,
+                                 float* obs, float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
+                                 int num_agents, int num_adversaries, int num_landmarks, int world_length,
+                                 int auto_reset, mappo_stream_t stream);
+
 /* ------------------------------------------------------------------- K16: Hanabi tables on the device ----
  * The batched Hanabi stepper of include/hanabi_batch.h (libhanabi_batch.so, host) with its tables in device memory: the
  * same rules, deal and encoder source (csrc/hanabi_rules.h), so for equal seeds and moves every row, reward, status and

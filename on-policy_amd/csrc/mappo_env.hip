@@ -649,6 +649,189 @@ __global__ void __launch_bounds__(64) tag_step_kernel(TagArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// simple_world_comm (scenarios/simple_world_comm.py): simple_tag's adversaries and good agents among L obstacles that
+// collide, followed in the landmark list by 2 pieces of food and 2 forests that do not.  Agent 0, the adversaries' leader,
+// says one of 4 words per step (one word per world, advanced in place like simple_speaker_listener's; -1: nothing said
+// since the restart) that every adversary observes.  Forests hide agents: agent i sees agent j iff i is the leader, both
+// are inside the same forest, or neither is inside any.  Not collaborative; the observation leaves as ONE row per world,
+// the agents' columns in agent order.
+constexpr int kWcObstacles = MAPPO_WORLD_COMM_MAX_OBSTACLES, kWcFood = 2, kWcForests = 2;
+constexpr int kWcFixed = kWcFood + kWcForests, kWcLandmarks = kWcObstacles + kWcFixed, kWcWords = 4;
+constexpr double kWcLandmarkScale = 0.8, kWcObstacleSize = 0.2, kWcFoodSize = 0.03, kWcForestSize = 0.3;
+constexpr double kWcCatch = 5.0, kWcFoodReward = 2.0;
+// (adversary, good agent)
+constexpr double kWcSize[2] = {0.075, 0.045}, kWcAccel[2] = {3.0, 4.0}, kWcMaxSpeed[2] = {1.0, 1.3};
+
+struct WorldCommArgs {
+    World s;                        // s.land: [N, L + 4, 2]; s.obs: [N, Nadv Da + G Dg], see the observation below
+    long long* comm;                // [N] the leader's last word, -1 = nothing said
+    const long long* act;           // [N, A + 1] (the leader's movement 0..4, its word 0..3, the others' movements)
+    int A, n_adv, L;                // L: obstacles
+};
+
+// landmark `which` of a list whose length is known only at run time, without indexing the registers
+template <int ML>
+__device__ __forceinline__ void pick_landmark(int which, const double (&lx)[ML], const double (&ly)[ML], double& x,
+                                              double& y) {
+    x = y = 0.0;
+#pragma unroll
+    for (int l = 0; l < ML; ++l) {
+        if (l == which) {
+            x = lx[l];
+            y = ly[l];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64) world_comm_step_kernel(WorldCommArgs a) {
+    const long long w = (long long)blockIdx.x * 64 + threadIdx.x;
+    const World& s = a.s;
+    if (w >= s.n) return;
+    const int A = a.A, L = a.L, n_adv = a.n_adv, Lt = a.L + kWcFixed;
+    constexpr int ML = kWcLandmarks;
+    double px[kMax], py[kMax], vx[kMax], vy[kMax], lx[ML], ly[ML];
+    load_world(s, w, A, Lt, px, py, vx, vy, lx, ly);
+    const ByKind size{n_adv, kWcSize[0], kWcSize[1]};
+    const long long* act = a.act + w * (A + 1);
+    // ---- the word becomes the communication state; forces: action (the acceleration acts twice, as in simple_tag) + soft
+    // contacts with agents and with the obstacles, the first L landmarks
+    long long comm = act[1];
+    {
+        const ByKind scale{n_adv, kWcAccel[0] * kWcAccel[0], kWcAccel[1] * kWcAccel[1]};
+        double fx[kMax], fy[kMax];
+#pragma unroll
+        for (int i = 0; i < kMax; ++i) {
+            if (i < A) action_force(act[i == 0 ? 0 : i + 1], fx[i], fy[i], scale.of(i));
+        }
+        add_contact_forces(A, size, px, py, fx, fy);
+        add_landmark_contact_forces(A, L, size, kWcObstacleSize, px, py, lx, ly, fx, fy);
+        integrate<true>(A, px, py, vx, vy, fx, fy, 0, ByKind{n_adv, kWcMaxSpeed[0], kWcMaxSpeed[1]});
+    }
+    long long t = s.t[w] + 1;
+    // ---- reward (simple_world_comm.py:154-199).  Adversary: +5 per (good agent, adversary) pair in touch, whoever the
+    // adversary, -0.1 x its distance to the nearest good agent.  Good agent: -5 per adversary that touches it, twice the
+    // penalty for leaving the screen, +2 per food it touches, +0.05 x its distance to the nearest food
+    {
+        double pa[kMax];
+#pragma unroll
+        for (int i = 0; i < kMax; ++i) pa[i] = 0.0;
+        int hits = 0;
+#pragma unroll
+        for (int j = 0; j < kMax; ++j) {
+            if (j >= n_adv || j >= A) continue;
+            double nearest = 1e300;
+#pragma unroll
+            for (int g = 0; g < kMax; ++g) {
+                if (g < n_adv || g >= A) continue;
+                const double dx = px[g] - px[j], dy = py[g] - py[j];
+                const double d = sqrt(dx * dx + dy * dy);
+                const bool touch = d < kWcSize[1] + kWcSize[0];
+                hits += touch;
+                if (touch) pa[g] -= kWcCatch;
+                nearest = fmin(nearest, d);
+            }
+            pa[j] = -0.1 * nearest;
+        }
+        double food_x[kWcFood], food_y[kWcFood];
+#pragma unroll
+        for (int f = 0; f < kWcFood; ++f) pick_landmark(L + f, lx, ly, food_x[f], food_y[f]);
+#pragma unroll
+        for (int i = 0; i < kMax; ++i) {
+            if (i >= A) continue;
+            if (i < n_adv) {
+                pa[i] += kWcCatch * hits;
+                continue;
+            }
+            int fed = 0;
+            double nearest = 1e300;
+#pragma unroll
+            for (int f = 0; f < kWcFood; ++f) {
+                const double dx = px[i] - food_x[f], dy = py[i] - food_y[f];
+                const double d = sqrt(dx * dx + dy * dy);
+                fed += d < kWcSize[1] + kWcFoodSize;
+                nearest = fmin(nearest, d);
+            }
+            pa[i] = pa[i] - 2 * (tag_bound(fabs(px[i])) + tag_bound(fabs(py[i]))) + kWcFoodReward * fed + 0.05 * nearest;
+        }
+        const bool restart = write_outcome(s, w, A, t, pa, 0.0, false);
+        if (restart) {
+            t = 0;
+            restart_from_fresh(s, w, A, Lt, kWcLandmarkScale, px, py, vx, vy, lx, ly);
+            comm = -1;
+        }
+        store_world(s, w, A, Lt, t, restart, px, py, vx, vy, lx, ly);
+        a.comm[w] = comm;
+    }
+    // ---- who is inside which forest of the (possibly restarted) world (simple_world_comm.py:232-240 is_collision), one bit
+    // per agent: the visibility mask and the in_forest columns both read these
+    unsigned in0 = 0, in1 = 0;
+    {
+        double f0x, f0y, f1x, f1y;
+        pick_landmark(L + kWcFood, lx, ly, f0x, f0y);
+        pick_landmark(L + kWcFood + 1, lx, ly, f1x, f1y);
+#pragma unroll
+        for (int i = 0; i < kMax; ++i) {
+            if (i >= A) continue;
+            const double reach = size.of(i) + kWcForestSize;
+            const double ax = px[i] - f0x, ay = py[i] - f0y, bx = px[i] - f1x, by = py[i] - f1y;
+            in0 |= (unsigned)(sqrt(ax * ax + ay * ay) < reach) << i;
+            in1 |= (unsigned)(sqrt(bx * bx + by * by) < reach) << i;
+        }
+    }
+    const unsigned open = ~(in0 | in1);
+    // ---- observation (simple_world_comm.py:225-288): own velocity, own position, the landmarks and the other agents
+    // relative to the agent -- (0, 0) for one it does not see --, then for an adversary the good agents' velocities (masked
+    // alike), its two in_forest flags as +-1 and the leader's word (one-hot); for a good agent the two flags and the other
+    // good agents' velocities (masked)
+    const int G = A - n_adv;
+    const int Dc = 4 + 2 * Lt + 2 * (A - 1) + 2, Da = Dc + 2 * G + kWcWords, Dg = Dc + 2 * (G - 1);
+    float* row = s.obs + w * ((long long)n_adv * Da + (long long)G * Dg);
+#pragma unroll
+    for (int i = 0; i < kMax; ++i) {
+        if (i >= A) continue;
+        float* o = i < n_adv ? row + i * Da : row + n_adv * Da + (i - n_adv) * Dg;
+        const bool i0 = (in0 >> i) & 1u, i1 = (in1 >> i) & 1u;
+        // bit j: agent i sees agent j
+        const unsigned sees = i == 0 ? ~0u : (i0 ? in0 : 0u) | (i1 ? in1 : 0u) | (i0 || i1 ? 0u : open);
+        int k = 0;
+        o[k++] = (float)vx[i];
+        o[k++] = (float)vy[i];
+        o[k++] = (float)px[i];
+        o[k++] = (float)py[i];
+#pragma unroll
+        for (int l = 0; l < ML; ++l) {
+            if (l >= Lt) continue;
+            o[k++] = (float)(lx[l] - px[i]);
+            o[k++] = (float)(ly[l] - py[i]);
+        }
+#pragma unroll
+        for (int j = 0; j < kMax; ++j) {
+            if (j >= A || j == i) continue;
+            const bool seen = (sees >> j) & 1u;
+            o[k++] = seen ? (float)(px[j] - px[i]) : 0.f;
+            o[k++] = seen ? (float)(py[j] - py[i]) : 0.f;
+        }
+        if (i >= n_adv) {
+            o[k++] = i0 ? 1.f : -1.f;
+            o[k++] = i1 ? 1.f : -1.f;
+        }
+#pragma unroll
+        for (int j = 0; j < kMax; ++j) {
+            if (j < n_adv || j >= A || j == i) continue;
+            const bool seen = (sees >> j) & 1u;
+            o[k++] = seen ? (float)vx[j] : 0.f;
+            o[k++] = seen ? (float)vy[j] : 0.f;
+        }
+        if (i < n_adv) {
+            o[k++] = i0 ? 1.f : -1.f;
+            o[k++] = i1 ? 1.f : -1.f;
+#pragma unroll
+            for (int word = 0; word < kWcWords; ++word) o[k++] = comm == word ? 1.f : 0.f;
+        }
+    }
+}
+
 // one thread per world, 64 to a block
 template <typename ArgsT>
 int launch_step(void (*kernel)(ArgsT), const ArgsT& a, mappo_stream_t stream_) {
@@ -735,4 +918,22 @@ extern "C" int mappo_simple_tag_step(double* pos, double* vel, double* landmarks
     const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
                   n_worlds, world_length, auto_reset};
     return launch_step(tag_step_kernel, TagArgs{s, i64(actions), num_agents, num_adversaries, num_landmarks}, stream_);
+}
+
+extern "C" int mappo_simple_world_comm_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* comm,
+                                            const int64_t* actions, const double* fresh_pos,
+                                            const double* fresh_landmarks, float* obs, float* rewards, uint8_t* dones,
+                                            double* per_agent, int64_t n_worlds, int num_agents, int num_adversaries,
+                                            int num_landmarks, int world_length, int auto_reset,
+                                            mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !comm || !actions || !obs || !rewards || !dones || !per_agent)
+        return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || num_adversaries < 1 || num_adversaries >= num_agents || num_landmarks < 1 || world_length < 1)
+        return MAPPO_E_SHAPE;
+    if (num_agents > kMax || num_landmarks > kWcObstacles) return MAPPO_E_TOO_MANY;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    return launch_step(world_comm_step_kernel,
+                       WorldCommArgs{s, i64(comm), i64(actions), num_agents, num_adversaries, num_landmarks}, stream_);
 }

@@ -230,6 +230,7 @@ SIGNATURES = {
     "mappo_simple_speaker_listener_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
     "mappo_simple_push_step": (_int, [_vp] * 13 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_tag_step": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _int, _vp]),
+    "mappo_simple_world_comm_step": (_int, [_vp] * 12 + [_i64, _int, _int, _int, _int, _int, _vp]),
     # K16: the eight int32 fields of hanabi_rules_t travel by value (``_RULES``)
     "mappo_hanabi_state_bytes": (_i64, _RULES),
     "mappo_hanabi_dims": (_int, _RULES + [_vp]),

@@ -1,7 +1,7 @@
 """What the multi-agent particle scenarios share: the physics constants (reference onpolicy/envs/mpe/core.py), the lazy
 ``infos`` of the device-resident envs, and ``TorchParticleWorlds``, the base class of worlds held as tensors on the
 policy's device.  A scenario (simple_spread.py, simple_reference.py,
-simple_speaker_listener.py, simple_push.py, simple_tag.py) adds its spaces, its extra state, its forces, reward and observation, and the one native call
+simple_speaker_listener.py, simple_push.py, simple_tag.py, simple_world_comm.py) adds its spaces, its extra state, its forces, reward and observation, and the one native call
 that is its step on a HIP device.
 """
 DT = 0.1

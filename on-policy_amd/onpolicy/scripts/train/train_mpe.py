@@ -11,8 +11,11 @@ spaces, so the separated runner only -- ``--share_policy`` -- with rmappo / mapp
 (envs/mpe/simple_push.py: one adversary and num_agents - 1 good agents with different observations and rewards of their
 own, 1 or 2 landmarks; the separated runner only, like simple_speaker_listener) and simple_tag (envs/mpe/simple_tag.py:
 ``--num_adversaries`` adversaries followed by ``--num_good_agents`` good agents, num_agents their sum; the separated
-runner only); every other case -- simple_reference, simple_speaker_listener, simple_push or simple_tag without the
-flag, any other scenario, and the eval envs of ``--use_eval`` in every case but one -- is built per worker from an external env tree (MAPPO_ENVS_PATH).  The exception:
+runner only) and simple_world_comm (envs/mpe/simple_world_comm.py: simple_tag's two kinds of agent among
+``--num_landmarks`` obstacles, two pieces of food and two forests that hide agents, the first adversary a leader with a
+MultiDiscrete action that says a word per step; 4 adversaries and 2 good agents where the two flags are not given; the
+separated runner only); every other case -- simple_reference, simple_speaker_listener, simple_push, simple_tag or
+simple_world_comm without the flag, any other scenario, and the eval envs of ``--use_eval`` in every case but one -- is built per worker from an external env tree (MAPPO_ENVS_PATH).  The exception:
 ``--use_device_eval`` (with ``--use_eval --use_device_env``, rmappo / mappo / ippo) builds the eval worlds of the
 device scenarios in-tree on the device too, and ``eval()`` then runs on tensors, its step as one captured graph launch
 (runner/shared/eval_graph.py).  wandb / setproctitle are optional.
@@ -38,6 +41,11 @@ Predator-prey on the device, three adversaries against one good agent (25-step e
         --num_agents 4 --num_adversaries 3 --num_good_agents 1 --num_landmarks 2 --n_rollout_threads 128 \
         --num_mini_batch 1 --episode_length 25 --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 \
         --critic_lr 7e-4 --share_policy --use_device_env
+Predator-prey with forests, food and a speaking leader on the device, four adversaries against two good agents:
+    python -m onpolicy.scripts.train.train_mpe --env_name MPE --algorithm_name rmappo --scenario_name simple_world_comm \
+        --num_agents 6 --num_adversaries 4 --num_good_agents 2 --num_landmarks 1 --n_rollout_threads 128 \
+        --num_mini_batch 1 --episode_length 25 --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 \
+        --critic_lr 7e-4 --share_policy --use_device_env
 """
 import argparse
 import sys
@@ -48,28 +56,33 @@ from onpolicy.envs.mpe.simple_reference import TorchSimpleReference
 from onpolicy.envs.mpe.simple_speaker_listener import TorchSimpleSpeakerListener
 from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread, VecSimpleSpread
 from onpolicy.envs.mpe.simple_tag import TorchSimpleTag
+from onpolicy.envs.mpe.simple_world_comm import TorchSimpleWorldComm
 from onpolicy.scripts.train import _launch
 
 
 # scenarios with an in-tree device implementation (--use_device_env; row f1): the worlds are held on the policy's device
 DEVICE_ENVS = {"simple_spread": TorchSimpleSpread, "simple_reference": TorchSimpleReference,
                "simple_speaker_listener": TorchSimpleSpeakerListener, "simple_push": TorchSimplePush,
-               "simple_tag": TorchSimpleTag}
+               "simple_tag": TorchSimpleTag, "simple_world_comm": TorchSimpleWorldComm}
 # ... of which these run under the separated runner (one policy per agent: the agents' spaces differ), the rest under the shared
-SEPARATED_DEVICE_ENVS = ("simple_speaker_listener", "simple_push", "simple_tag")
+SEPARATED_DEVICE_ENVS = ("simple_speaker_listener", "simple_push", "simple_tag", "simple_world_comm")
 TAG_DEFAULTS = (3, 1)       # adversaries, good agents where --num_adversaries / --num_good_agents are not given
+WORLD_COMM_DEFAULTS = (4, 2)    # ... of simple_world_comm: the reference's documented counts
+# the scenarios whose agents are adversaries followed by good agents
+KIND_DEFAULTS = {"simple_tag": TAG_DEFAULTS, "simple_world_comm": WORLD_COMM_DEFAULTS}
 
 
 def tag_counts(all_args):
-    """-> (adversaries, good agents) of a simple_tag run."""
-    return (getattr(all_args, "num_adversaries", TAG_DEFAULTS[0]), getattr(all_args, "num_good_agents", TAG_DEFAULTS[1]))
+    """-> (adversaries, good agents) of a simple_tag or simple_world_comm run."""
+    adv, good = KIND_DEFAULTS.get(all_args.scenario_name, TAG_DEFAULTS)
+    return getattr(all_args, "num_adversaries", adv), getattr(all_args, "num_good_agents", good)
 
 
 def make_train_env(all_args, n_threads=None, seed_offset=0, device=None):
     n = all_args.n_rollout_threads if n_threads is None else n_threads
     seed_offset += 1000 * getattr(all_args, "rollout_thread_offset", 0)      # data-parallel rank: its own worlds
     if device is not None and all_args.scenario_name in DEVICE_ENVS:
-        extra = {"num_adversaries": tag_counts(all_args)[0]} if all_args.scenario_name == "simple_tag" else {}
+        extra = {"num_adversaries": tag_counts(all_args)[0]} if all_args.scenario_name in KIND_DEFAULTS else {}
         return DEVICE_ENVS[all_args.scenario_name](n, all_args.num_agents, all_args.num_landmarks,
                                                    all_args.episode_length, seed=all_args.seed + seed_offset,
                                                    device=device, **extra)
@@ -96,7 +109,7 @@ def parse_args(args, parser):
     parser.add_argument('--num_agents', type=int, default=2, help="number of players")
     parser.add_argument('--use_device_env', action='store_true', default=False,
                         help="simple_spread or simple_reference (shared-policy runner) or simple_speaker_listener, "
-                             "simple_push or simple_tag (separated runner: --share_policy) with the training worlds held as "
+                             "simple_push, simple_tag or simple_world_comm (separated runner: --share_policy) with the training worlds held as "
                              "tensors on the policy's device: no per-step host round trip")
     # (argparse.SUPPRESS: the attribute exists only when the flag is given, so a default parse carries the reference's flags
     # and --use_device_env, nothing else; readers use getattr(args, "fused_multi_loss", False))
@@ -111,9 +124,10 @@ def parse_args(args, parser):
                              "(MAPPO_EVAL_GRAPH=0: the eager tensor loop)")
     # (SUPPRESS as above; the external env tree's simple_tag reads the same two attributes)
     parser.add_argument('--num_adversaries', type=int, default=argparse.SUPPRESS,
-                        help="simple_tag: agents 0 .. num_adversaries - 1 chase the others (3 where not given)")
+                        help="simple_tag / simple_world_comm: agents 0 .. num_adversaries - 1 chase the others (3 / 4 where "
+                             "not given)")
     parser.add_argument('--num_good_agents', type=int, default=argparse.SUPPRESS,
-                        help="simple_tag: the agents that are chased (1 where not given); with --use_device_env "
+                        help="simple_tag / simple_world_comm: the agents that are chased (1 / 2 where not given); with --use_device_env "
                              "num_agents = num_adversaries + num_good_agents")
     return parser.parse_known_args(args)[0]
 
@@ -143,12 +157,15 @@ def main(args):
             raise NotImplementedError("--use_device_env: simple_push colours landmark l on channel l + 1 of three, so "
                                       "--num_landmarks is 1 or 2 (the reference fails at 3), not %d"
                                       % all_args.num_landmarks)
-        if scenario == "simple_tag":
+        if scenario in KIND_DEFAULTS:
             adv, good = tag_counts(all_args)
             if adv < 1 or good < 1 or all_args.num_agents != adv + good:
-                raise NotImplementedError("--use_device_env: simple_tag needs num_agents = num_adversaries + "
+                raise NotImplementedError("--use_device_env: %s needs num_agents = num_adversaries + "
                                           "num_good_agents with at least one of each, not %d = %d + %d"
-                                          % (all_args.num_agents, adv, good))
+                                          % (scenario, all_args.num_agents, adv, good))
+        if scenario == "simple_world_comm" and all_args.num_landmarks < 1:
+            raise NotImplementedError("--use_device_env: simple_world_comm needs at least one obstacle (--num_landmarks), "
+                                      "not %d" % all_args.num_landmarks)
     envs = make_train_env(all_args, device=device if all_args.use_device_env else None)
     eval_envs = make_train_env(all_args, all_args.n_eval_rollout_threads, 50000,
                                device=device if device_eval else None) if all_args.use_eval else None

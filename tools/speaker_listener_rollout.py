@@ -2,7 +2,8 @@
 """One 25-step rollout of the reference's train_mpe_comm.sh (MPE simple_speaker_listener, 2 agents, 3 landmarks, rmappo,
 128 rollout threads, hidden 64, one policy per agent) -- or, with ``--scenario simple_push --num_agents A --num_landmarks
 L``, of keep-away at the same script family's shape, or, with ``--scenario simple_tag --num_adversaries V
---num_good_agents G --num_landmarks L``, of predator-prey -- on one MI355X with the worlds on the device (--use_device_env),
+--num_good_agents G --num_landmarks L``, of predator-prey, or, with ``--scenario simple_world_comm`` and the same three
+flags, of predator-prey with forests, food and a speaking leader -- on one MI355X with the worlds on the device (--use_device_env),
 timed two ways in the same process, alternating: the separated runner's eager device loop (collect -> envs.step ->
 insert: what MAPPO_ROLLOUT_GRAPH=0 runs) and the captured step (runner/separated/rollout_graph.py: one graph launch + one
 slab write per agent).  Both start every rollout from the buffers' row 0 and leave the same fields behind.
@@ -10,6 +11,8 @@ slab write per agent).  Both start every rollout from the buffers' row 0 and lea
     python tools/speaker_listener_rollout.py [--reps 30] [--warmup 5] [--commit HASH] [--out file.json [--append]]
     python tools/speaker_listener_rollout.py --scenario simple_push --num_agents 3 --num_landmarks 2 ...
     python tools/speaker_listener_rollout.py --scenario simple_tag --num_adversaries 3 --num_good_agents 1 ...
+    python tools/speaker_listener_rollout.py --scenario simple_world_comm --num_adversaries 4 --num_good_agents 2 \
+        --num_landmarks 1 ...
 
 Per way: median, quartiles, 10th / 90th percentile and range of the rollout's wall time (host clock around work that ends
 in a device synchronise) over ``--reps`` rollouts after ``--warmup`` untimed ones.  ``spread_ms`` is the larger of the two
@@ -39,10 +42,10 @@ def summary(ms):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenario", default="simple_speaker_listener", choices=("simple_speaker_listener", "simple_push", "simple_tag"))
-    ap.add_argument("--num_agents", type=int, default=2, help="simple_tag: --num_adversaries + --num_good_agents instead")
-    ap.add_argument("--num_adversaries", type=int, default=3, help="simple_tag only")
-    ap.add_argument("--num_good_agents", type=int, default=1, help="simple_tag only")
+    ap.add_argument("--scenario", default="simple_speaker_listener", choices=("simple_speaker_listener", "simple_push", "simple_tag", "simple_world_comm"))
+    ap.add_argument("--num_agents", type=int, default=2, help="simple_tag / simple_world_comm: --num_adversaries + --num_good_agents instead")
+    ap.add_argument("--num_adversaries", type=int, default=3, help="simple_tag / simple_world_comm only")
+    ap.add_argument("--num_good_agents", type=int, default=1, help="simple_tag / simple_world_comm only")
     ap.add_argument("--num_landmarks", type=int, default=None, help="default: 3 for simple_speaker_listener, 2 otherwise")
     ap.add_argument("--threads", type=int, default=128)
     ap.add_argument("--episode_length", type=int, default=25)
@@ -56,7 +59,8 @@ if __name__ == "__main__":
     opt = ap.parse_args()
     landmarks = opt.num_landmarks if opt.num_landmarks is not None else (3 if opt.scenario == "simple_speaker_listener" else 2)
     tag = ["--num_adversaries", str(opt.num_adversaries), "--num_good_agents", str(opt.num_good_agents)]
-    if opt.scenario == "simple_tag":
+    by_kind = opt.scenario in ("simple_tag", "simple_world_comm")        # adversaries followed by good agents
+    if by_kind:
         opt.num_agents = opt.num_adversaries + opt.num_good_agents
     os.environ.setdefault("MAPPO_RESULTS_DIR", tempfile.mkdtemp())
     os.environ["MAPPO_ROLLOUT_GRAPH"] = "1"
@@ -70,7 +74,7 @@ if __name__ == "__main__":
             "--n_training_threads", "1", "--n_rollout_threads", str(N), "--num_mini_batch", "1",
             "--episode_length", str(T), "--num_env_steps", str(T * N), "--ppo_epoch", "15", "--gain", "0.01",
             "--lr", "7e-4", "--critic_lr", "7e-4", "--share_policy", "--hidden_size", str(opt.hidden_size), "--use_wandb",
-            "--log_interval", "1000", "--save_interval", "1000", "--use_device_env"] + (tag if opt.scenario == "simple_tag" else [])
+            "--log_interval", "1000", "--save_interval", "1000", "--use_device_env"] + (tag if by_kind else [])
     runner = train_mpe.main(argv)           # one whole iteration: builds everything, captures the step, one train()
     graph = runner.rollout_graph
     assert graph is not None and graph.graph is not None, "the rollout step was not captured"
@@ -111,7 +115,7 @@ if __name__ == "__main__":
     launches, activities, why = None, None, None
     spread = max(e["p90_ms"] - e["p10_ms"], g["p90_ms"] - g["p10_ms"])
 
-    agents = ("%d agents" % opt.num_agents if opt.scenario != "simple_tag" else
+    agents = ("%d agents" % opt.num_agents if not by_kind else
               "%d adversaries against %d good agents" % (opt.num_adversaries, opt.num_good_agents))
     out = {"config": "%s: MPE %s, %s, %d landmarks, %s, n_rollout_threads=%d, "
                      "episode_length=%d, hidden_size=%d, one policy per agent, 1 x MI355X, worlds on the device"
