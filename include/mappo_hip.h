@@ -808,6 +808,20 @@ int mappo_simple_spread_step(double* pos, double* vel, double* landmarks, int64_
                              uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents, int num_landmarks,
                              int world_length, int auto_reset, mappo_stream_t stream);
 
+/* ------------------------------------------------- K11 wide: simple_spread worlds of up to 64 entities ----
+ * The step of mappo_simple_spread_step -- its operands, its state updated in place, its outputs, its return codes -- for
+ * 1 <= A, L <= MAPPO_ENV_WIDE_MAX_ENTITIES.  Where K11 keeps a world in one thread's registers, here the lanes of a wave
+ * lie along a world's entities (32 lanes per world while A, L <= 32, else 64) and the world's image in LDS; the
+ * observation leaves as 8-byte stores side by side along a row.  The sums over a world (the landmarks' cover, the
+ * agents' total) are added in a fixed butterfly order rather than K11's ascending one, so state and per_agent agree
+ * with K11 to rounding (1e-12), not bit for bit; a launch repeats itself bit for bit.  MAPPO_E_SHAPE for A < 1 or
+ * L < 1, MAPPO_E_TOO_MANY for A > 64 or L > 64; nothing is launched or written then. */
+#define MAPPO_ENV_WIDE_MAX_ENTITIES 64
+int mappo_simple_spread_step_wide(double* pos, double* vel, double* landmarks, int64_t* t, const int64_t* actions,
+                                  const double* fresh_pos, const double* fresh_landmarks, float* obs, float* rewards,
+                                  uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents,
+                                  int num_landmarks, int world_length, int auto_reset, mappo_stream_t stream);
+
 /* ----------------------------------------------------- K11 family: simple_reference worlds on the device ----
  * One env step of `n_worlds` referential-communication worlds (reference onpolicy/envs/mpe/scenarios/simple_reference.py,
  * environment.py:115-255, core.py:207-288; 2 agents, 3 landmarks, no contacts) as one launch.  State is updated in

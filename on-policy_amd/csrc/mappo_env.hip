@@ -12,7 +12,8 @@
 // own forces, extra state, reward and observation.  A world's entities are plain arrays px / py / vx / vy [agents] and
 // lx / ly [landmarks] that the helpers take by reference (separate arrays: one aggregate of all six does not come apart
 // into registers at 16 entities); they are templated on the array bound so that a scenario with fixed counts keeps them
-// at compile time and one with runtime counts stays fully unrolled.
+// at compile time and one with runtime counts stays fully unrolled.  That design ends at kMax entities, where the register
+// file is full; simple_spread worlds of up to 64 have a second kernel with the lanes along the entities (K11 wide, below).
 #include <hip/hip_runtime.h>
 
 #include "../../include/mappo_hip.h"
@@ -291,6 +292,138 @@ __global__ void __launch_bounds__(64) spread_step_kernel(Args a) {
             o[k++] = (float)(py[j] - py[i]);
         }
         for (int z = 0; z < 2 * (A - 1); ++z) o[k++] = 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// simple_spread past kMax entities (K11 wide): the opposite work split.  LPW lanes own a world, lane e its agent e and
+// its landmark e, and the world's image lies in LDS where the pair loops read it (all lanes of a world read one address:
+// a broadcast).  A and L are runtime values up to kWideMax and nothing is unrolled over entities, so the register file
+// no longer bounds the world; the observation, 2 L + 4 A floats per agent, leaves as float2 stores that the world's
+// lanes lay side by side along a row.  The arithmetic is spread_step_kernel's, expression by expression, but for the two
+// sums over the world (cover, total), which are xor butterflies here: a fixed order, the same bits in every lane.
+constexpr int kWideMax = MAPPO_ENV_WIDE_MAX_ENTITIES, kWideThreads = 256;
+
+// the sum of x over the LPW lanes of a world, in every one of them
+template <int LPW>
+__device__ __forceinline__ double world_sum(double x) {
+#pragma unroll
+    for (int stride = 1; stride < LPW; stride *= 2) x += __shfl_xor(x, stride);
+    return x;
+}
+
+template <int LPW>
+__global__ void __launch_bounds__(kWideThreads) spread_step_wide_kernel(Args a) {
+    static_assert(LPW == 32 || LPW == 64, "a world is half a wave or a whole one");
+    // one double2 per lane and array: the image of world slot k is [k * LPW, (k + 1) * LPW)
+    __shared__ double2 s_pos[kWideThreads], s_vel[kWideThreads], s_land[kWideThreads];
+    const World& s = a.s;
+    const int A = a.A, L = a.L;
+    const int tid = threadIdx.x, lane = tid % LPW, base = tid - lane;
+    const long long w = (long long)blockIdx.x * (kWideThreads / LPW) + tid / LPW;
+    // no thread leaves before the last barrier: a world past n, and a lane past the world's entities, is predicated
+    const bool live = w < s.n, is_agent = live && lane < A, is_land = live && lane < L;
+    const long long ia = w * A + lane, il = w * L + lane;
+    double2 p = {0.0, 0.0}, v = {0.0, 0.0}, l = {0.0, 0.0};
+    long long mv = 0, t = 0;
+    if (is_agent) {
+        p = reinterpret_cast<const double2*>(s.pos)[ia];
+        v = reinterpret_cast<const double2*>(s.vel)[ia];
+        mv = a.act[ia];
+    }
+    if (is_land) l = reinterpret_cast<const double2*>(s.land)[il];
+    if (live) t = s.t[w] + 1;
+    s_pos[tid] = p;
+    s_land[tid] = l;
+    __syncthreads();
+    // ---- forces: action + soft contacts (add_contact_forces for one agent), then integrate's expressions
+    if (is_agent) {
+        double fx, fy, sx = 0.0, sy = 0.0;
+        action_force(mv, fx, fy);
+        for (int j = 0; j < A; ++j) {
+            if (j == lane) continue;
+            const double2 o = s_pos[base + j];
+            contact_force(p.x - o.x, p.y - o.y, kSize + kSize, sx, sy);
+        }
+        fx += sx;
+        fy += sy;
+        v.x = v.x * (1 - kDamping) + fx * kDt;
+        v.y = v.y * (1 - kDamping) + fy * kDt;
+        p.x = p.x + v.x * kDt;
+        p.y = p.y + v.y * kDt;
+    }
+    __syncthreads();        // every lane has read the old positions
+    s_pos[tid] = p;
+    __syncthreads();
+    // ---- reward: lane l the closest agent's distance to its landmark, lane i its contacts (itself included)
+    double best = 0.0;
+    if (is_land) {
+        best = 1e300;
+        for (int i = 0; i < A; ++i) {
+            const double2 o = s_pos[base + i];
+            const double dx = o.x - l.x, dy = o.y - l.y;
+            best = fmin(best, sqrt(dx * dx + dy * dy));
+        }
+    }
+    const double cover = -world_sum<LPW>(best);
+    double pa = 0.0;
+    if (is_agent) {
+        int hits = 0;
+        for (int j = 0; j < A; ++j) {
+            const double2 o = s_pos[base + j];
+            const double dx = p.x - o.x, dy = p.y - o.y;
+            hits += sqrt(dx * dx + dy * dy) < 2 * kSize;
+        }
+        pa = cover - hits;
+    }
+    const double total = world_sum<LPW>(pa);
+    // ---- outcome and restart (write_outcome, restart_from_fresh, store_world for one entity)
+    const bool done = t >= s.world_length, restart = done && s.auto_reset;
+    if (is_agent) {
+        s.per_agent[ia] = pa;
+        s.rew[ia] = (float)total;
+        s.done[ia] = done ? 1 : 0;
+        if (restart) {
+            p = reinterpret_cast<const double2*>(s.fresh_pos)[ia];
+            v = double2{0.0, 0.0};
+        }
+        reinterpret_cast<double2*>(s.pos)[ia] = p;
+        reinterpret_cast<double2*>(s.vel)[ia] = v;
+    }
+    if (is_land && restart) {
+        l = reinterpret_cast<const double2*>(s.fresh_land)[il];
+        reinterpret_cast<double2*>(s.land)[il] = l;
+    }
+    if (live && lane == 0) s.t[w] = restart ? 0 : t;
+    __syncthreads();        // every lane has counted its contacts
+    s_pos[tid] = p;
+    s_vel[tid] = v;
+    s_land[tid] = l;
+    __syncthreads();
+    // ---- observation of the (possibly restarted) world.  A row is Do / 2 pairs (x, y): vel_i, pos_i, the landmarks and
+    // the other agents relative to agent i, A - 1 silent channels.  The world's lanes walk the rows together, lane k
+    // writing the pairs k, k + LPW, ... of each
+    const int pairs = 2 + L + 2 * (A - 1);
+    float2* row = reinterpret_cast<float2*>(s.obs) + w * A * pairs;
+    for (int i = 0; i < A; ++i, row += pairs) {
+        const double2 me = s_pos[base + i];
+        for (int q = lane; q < pairs; q += LPW) {
+            double2 o = {0.0, 0.0};
+            if (q == 0) {
+                o = s_vel[base + i];
+            } else if (q == 1) {
+                o = me;
+            } else if (q < 2 + L) {
+                const double2 e = s_land[base + q - 2];
+                o = double2{e.x - me.x, e.y - me.y};
+            } else if (q < 2 + L + A - 1) {
+                int j = q - 2 - L;
+                j += j >= i;
+                const double2 e = s_pos[base + j];
+                o = double2{e.x - me.x, e.y - me.y};
+            }
+            if (live) row[q] = float2{(float)o.x, (float)o.y};
+        }
     }
 }
 
@@ -856,6 +989,31 @@ extern "C" int mappo_simple_spread_step(double* pos, double* vel, double* landma
     const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
                   n_worlds, world_length, auto_reset};
     return launch_step(spread_step_kernel, Args{s, i64(actions), num_agents, num_landmarks}, stream_);
+}
+
+// LPW lanes per world, kWideThreads / LPW worlds per workgroup
+template <int LPW>
+int launch_wide(const Args& a, mappo_stream_t stream_) {
+    constexpr int worlds = kWideThreads / LPW;
+    hipLaunchKernelGGL(spread_step_wide_kernel<LPW>, dim3((unsigned)((a.s.n + worlds - 1) / worlds)), dim3(kWideThreads), 0,
+                       static_cast<hipStream_t>(stream_), a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mappo_simple_spread_step_wide(double* pos, double* vel, double* landmarks, int64_t* t,
+                                             const int64_t* actions, const double* fresh_pos,
+                                             const double* fresh_landmarks, float* obs, float* rewards, uint8_t* dones,
+                                             double* per_agent, int64_t n_worlds, int num_agents, int num_landmarks,
+                                             int world_length, int auto_reset, mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !actions || !obs || !rewards || !dones || !per_agent) return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || num_agents < 1 || num_landmarks < 1 || world_length < 1) return MAPPO_E_SHAPE;
+    if (num_agents > kWideMax || num_landmarks > kWideMax) return MAPPO_E_TOO_MANY;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    const Args a{s, i64(actions), num_agents, num_landmarks};
+    // two worlds to a wave where both entity counts fit half of one
+    return num_agents <= 32 && num_landmarks <= 32 ? launch_wide<32>(a, stream_) : launch_wide<64>(a, stream_);
 }
 
 extern "C" int mappo_simple_reference_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goals,

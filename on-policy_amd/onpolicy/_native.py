@@ -226,6 +226,7 @@ SIGNATURES = {
     "mappo_linear512_wgrad_workspace_floats": (_i64, [_int]),
     "mappo_linear512_wgrad": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "mappo_simple_spread_step": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
+    "mappo_simple_spread_step_wide": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_reference_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
     "mappo_simple_speaker_listener_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
     "mappo_simple_push_step": (_int, [_vp] * 13 + [_i64, _int, _int, _int, _int, _vp]),

@@ -14,6 +14,8 @@ operations, so a rollout step costs one numpy pass instead of ``n_threads`` pipe
 VecEnv protocol (reference onpolicy/envs/env_wrappers.py:235-298): ``reset() -> obs [N, A, Do]``,
 ``step(one_hot_actions [N, A, 5]) -> obs, rewards [N, A, 1], dones [N, A], infos``.
 """
+import os
+
 import numpy as np
 
 from onpolicy.envs.spaces import Box, Discrete
@@ -106,8 +108,12 @@ class VecSimpleSpread(object):
 class TorchSimpleSpread(TorchParticleWorlds):
     """The same worlds as ``VecSimpleSpread`` held as tensors on ``device`` (``TorchParticleWorlds``): with the policy,
     the rollout buffer and the env on the GPU, a rollout step moves nothing over PCIe.  Actions: the integer tensor
-    [N, A, 1] as it comes out of the policy, or one-hot [N, A, 5].  The kernel path (K11, ``mappo_simple_spread_step``:
-    30 us per step at 4096 worlds against 140 ms as tensor operations) takes up to 16 agents and 16 landmarks."""
+    [N, A, 1] as it comes out of the policy, or one-hot [N, A, 5].  The kernel path takes up to 64 agents and 64
+    landmarks: K11 (``mappo_simple_spread_step``: a thread per world, 30 us per step at 4096 worlds against 140 ms as
+    tensor operations) up to 16 of each, K11 wide (``mappo_simple_spread_step_wide``: the lanes of a wave along a world's
+    entities) from there on, and for every shape it takes where ``MAPPO_SPREAD_WIDE=1`` was set when the worlds were built.
+    Past 64 the tensor path runs."""
+    KERNEL_MAX, WIDE_MAX = 16, 64       # MAPPO_ENV_MAX_ENTITIES, MAPPO_ENV_WIDE_MAX_ENTITIES
 
     def __init__(self, n_threads, num_agents=3, num_landmarks=None, episode_length=25, seed=1, auto_reset=True,
                  device="cpu"):
@@ -116,10 +122,11 @@ class TorchSimpleSpread(TorchParticleWorlds):
         super().__init__(n_threads, a, l, episode_length, seed, auto_reset, device, obs_dim=4 + 2 * l + 4 * (a - 1),
                          action_space=lambda: Discrete(5))
         self._others = ~self._torch.eye(self.a, dtype=self._torch.bool, device=self.device)
+        self._wide = max(self.a, self.l) > self.KERNEL_MAX or os.environ.get("MAPPO_SPREAD_WIDE") == "1"
 
     @property
     def graph_safe(self):
-        return self.device.type == "cuda" and self.a <= 16 and self.l <= 16
+        return self.device.type == "cuda" and max(self.a, self.l) <= self.WIDE_MAX
 
     def _obs(self):
         torch = self._torch
@@ -160,7 +167,8 @@ class TorchSimpleSpread(TorchParticleWorlds):
         from onpolicy import _native
         p = _native.ptr
         fresh_pos, fresh_land = fresh or (None, None)
-        _native.check(_native.lib().mappo_simple_spread_step(
+        name = "mappo_simple_spread_step_wide" if self._wide else "mappo_simple_spread_step"
+        _native.check(getattr(_native.lib(), name)(
             p(self.pos), p(self.vel), p(self.landmarks), p(self.t), p(idx), p(fresh_pos), p(fresh_land), p(obs),
             p(rewards), p(dones), p(per_agent), self.n, self.a, self.l, self.world_length, int(self.auto_reset),
-            _native.stream_of(self.device)), "mappo_simple_spread_step")
+            _native.stream_of(self.device)), name)

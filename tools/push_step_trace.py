@@ -2,11 +2,13 @@
 """Steps device-resident simple_push worlds through their kernel path (``mappo_simple_push_step``, one launch per step)
 -- or, with ``--scenario simple_tag --num_adversaries V``, simple_tag worlds through ``mappo_simple_tag_step``, or, with
 ``--scenario simple_world_comm --num_adversaries V``, simple_world_comm worlds (``--num_landmarks`` obstacles) through
-``mappo_simple_world_comm_step`` -- and nothing else, for a kernel-trace run of its own:
+``mappo_simple_world_comm_step``, or, with ``--scenario simple_spread``, simple_spread worlds through
+``mappo_simple_spread_step`` up to 16 agents and landmarks and ``mappo_simple_spread_step_wide`` past that (and for every
+shape up to 64 with ``MAPPO_SPREAD_WIDE=1`` in the environment) -- and nothing else, for a kernel-trace run of its own:
 
     rocprofv3 --kernel-trace --stats -f csv -d out -o push -- python tools/push_step_trace.py --worlds 4096
 
-The trace's ``push_step_kernel`` (``tag_step_kernel``, ``world_comm_step_kernel``) row is the step kernel's own time at that number of worlds (the generator draws of a
+The trace's ``push_step_kernel`` (``tag_step_kernel``, ``world_comm_step_kernel``, ``spread_step_kernel``, ``spread_step_wide_kernel<32 | 64>``) row is the step kernel's own time at that number of worlds (the generator draws of a
 step and the action tensor are separate kernels in the same trace).  Prints one JSON line with the shape and the wall
 time per step as the host sees it.
 """
@@ -21,7 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "on-policy_amd"))
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenario", default="simple_push", choices=("simple_push", "simple_tag", "simple_world_comm"))
+    ap.add_argument("--scenario", default="simple_push", choices=("simple_push", "simple_tag", "simple_world_comm", "simple_spread"))
     ap.add_argument("--num_adversaries", type=int, default=3, help="simple_tag / simple_world_comm only: of --num_agents")
     ap.add_argument("--worlds", type=int, default=128)
     ap.add_argument("--num_agents", type=int, default=2)
@@ -30,6 +32,7 @@ if __name__ == "__main__":
     opt = ap.parse_args()
     import torch
     from onpolicy.envs.mpe.simple_push import TorchSimplePush
+    from onpolicy.envs.mpe.simple_spread import TorchSimpleSpread
     from onpolicy.envs.mpe.simple_tag import TorchSimpleTag
     from onpolicy.envs.mpe.simple_world_comm import TorchSimpleWorldComm
     assert torch.cuda.is_available(), "a trace needs the GPU"
@@ -37,6 +40,8 @@ if __name__ == "__main__":
     if opt.scenario in ("simple_tag", "simple_world_comm"):
         cls = TorchSimpleTag if opt.scenario == "simple_tag" else TorchSimpleWorldComm
         env = cls(opt.worlds, opt.num_agents, opt.num_landmarks, seed=1, device=dev, num_adversaries=opt.num_adversaries)
+    elif opt.scenario == "simple_spread":
+        env = TorchSimpleSpread(opt.worlds, opt.num_agents, opt.num_landmarks, seed=1, device=dev)
     else:
         env = TorchSimplePush(opt.worlds, opt.num_agents, opt.num_landmarks, seed=1, device=dev)
     assert env.graph_safe
