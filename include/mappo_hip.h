@@ -907,6 +907,22 @@ int mappo_simple_tag_step(double* pos, double* vel, double* landmarks, int64_t* 
                           uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents, int num_adversaries,
                           int num_landmarks, int world_length, int auto_reset, mappo_stream_t stream);
 
+/* --------------------------------------------------- K11 wide: simple_tag worlds of up to 64 entities ----
+ * The step of mappo_simple_tag_step -- its operands, its state updated in place, its outputs, its return codes -- for
+ * A = num_agents in 2..MAPPO_ENV_WIDE_MAX_ENTITIES and L = num_landmarks in 1..MAPPO_ENV_WIDE_MAX_ENTITIES.  Where the
+ * thin kernel keeps a world in one thread's registers, here the lanes of a wave lie along a world's entities (32 lanes
+ * per world while A, L <= 32, else 64) and the world's image in LDS; the observation row of a world, whose agent
+ * segments have two widths, leaves as 8-byte stores that the world's lanes lay side by side along the whole row.  The
+ * arithmetic is the thin kernel's in its order (agent contacts, then landmark contacts, the speed clamp before the
+ * position); the only value that crosses lanes is the integer catch count, so no sum is reordered against it.
+ * MAPPO_E_SHAPE for Nadv outside 1..A-1 or L < 1, MAPPO_E_TOO_MANY for A > 64 or L > 64; nothing is launched or
+ * written then. */
+int mappo_simple_tag_step_wide(double* pos, double* vel, double* landmarks, int64_t* t, const int64_t* actions,
+                               const double* fresh_pos, const double* fresh_landmarks, float* obs, float* rewards,
+                               uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents,
+                               int num_adversaries, int num_landmarks, int world_length, int auto_reset,
+                               mappo_stream_t stream);
+
 /* ---------------------------------------------------- K11 family: simple_world_comm worlds on the device ----
  * One env step of `n_worlds` worlds of predator-prey with forests, food and a speaking leader (reference
  * onpolicy/envs/mpe/scenarios/simple_world_comm.py, environment.py:54-98 and :115-255, core.py:207-321; A = num_agents in

@@ -783,6 +783,153 @@ __global__ void __launch_bounds__(64) tag_step_kernel(TagArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// simple_tag past kMax agents or kTagLandmarks landmarks (K11 wide for predator-prey): spread_step_wide_kernel's work
+// split -- LPW lanes own a world, lane e its agent e and its landmark e, the world's image in LDS, pair loops over the
+// runtime counts that read one LDS address per world -- with tag_step_kernel's arithmetic, expression by expression and
+// in its order: a lane's kind (adversary: lane < n_adv) picks its radius, acceleration and top speed, the contacts with
+// the agents are summed before those with the landmarks, and the speed is clamped before the position moves.  The one
+// quantity that crosses lanes is the catch count, an integer and so exact in any order: no sum here runs in another
+// order than the thin kernel's (the tensor step's do, torch's `sum` being a tree).  The observation is ONE row per world
+// whose agent segments have two widths; the world's lanes walk the concatenated row, not agent by agent: lane k writes
+// the row's pairs k, k + LPW, ... and decodes each flat pair index into (agent, field), one integer division a pair, so
+// that every trip but the row's last has all lanes busy and a wave's stores stay contiguous across the segments'
+// borders (a loop over agents leaves the lanes past a segment's last pair idle once per agent: 24 of 32 at 3 against 1
+// among 2 landmarks, 47 of 192 at 48 against 16 among 64).
+template <int LPW>
+__global__ void __launch_bounds__(kWideThreads) tag_step_wide_kernel(TagArgs a) {
+    static_assert(LPW == 32 || LPW == 64, "a world is half a wave or a whole one");
+    // one double2 per lane and array: the image of world slot k is [k * LPW, (k + 1) * LPW)
+    __shared__ double2 s_pos[kWideThreads], s_vel[kWideThreads], s_land[kWideThreads];
+    const World& s = a.s;
+    const int A = a.A, L = a.L, n_adv = a.n_adv, G = A - n_adv;
+    const int tid = threadIdx.x, lane = tid % LPW, base = tid - lane;
+    const long long w = (long long)blockIdx.x * (kWideThreads / LPW) + tid / LPW;
+    // no thread leaves before the last barrier: a world past n, and a lane past the world's entities, is predicated
+    const bool live = w < s.n, is_agent = live && lane < A, is_land = live && lane < L, adversary = lane < n_adv;
+    const long long ia = w * A + lane, il = w * L + lane;
+    double2 p = {0.0, 0.0}, v = {0.0, 0.0}, l = {0.0, 0.0};
+    long long mv = 0, t = 0;
+    if (is_agent) {
+        p = reinterpret_cast<const double2*>(s.pos)[ia];
+        v = reinterpret_cast<const double2*>(s.vel)[ia];
+        mv = a.act[ia];
+    }
+    if (is_land) l = reinterpret_cast<const double2*>(s.land)[il];
+    if (live) t = s.t[w] + 1;
+    s_pos[tid] = p;
+    s_land[tid] = l;
+    __syncthreads();
+    // ---- forces: action (accel^2) + soft contacts with the agents, then with the landmarks (add_contact_forces and
+    // add_landmark_contact_forces for one agent), then integrate<true>'s expressions
+    if (is_agent) {
+        const ByKind size{n_adv, kTagSize[0], kTagSize[1]};
+        const double radius = size.of(lane), accel = adversary ? kTagAccel[0] : kTagAccel[1];
+        double fx, fy, sx = 0.0, sy = 0.0;
+        action_force(mv, fx, fy, accel * accel);
+        for (int j = 0; j < A; ++j) {
+            if (j == lane) continue;
+            const double2 o = s_pos[base + j];
+            contact_force(p.x - o.x, p.y - o.y, radius + size.of(j), sx, sy);
+        }
+        fx += sx;
+        fy += sy;
+        sx = sy = 0.0;
+        for (int k = 0; k < L; ++k) {
+            const double2 o = s_land[base + k];
+            contact_force(p.x - o.x, p.y - o.y, radius + kTagLandmarkSize, sx, sy);
+        }
+        fx += sx;
+        fy += sy;
+        v.x = v.x * (1 - kDamping) + fx * kDt;
+        v.y = v.y * (1 - kDamping) + fy * kDt;
+        const double speed = sqrt(v.x * v.x + v.y * v.y), top = adversary ? kTagMaxSpeed[0] : kTagMaxSpeed[1];
+        if (speed > top) {
+            v.x = v.x / speed * top;
+            v.y = v.y / speed * top;
+        }
+        p.x = p.x + v.x * kDt;
+        p.y = p.y + v.y * kDt;
+    }
+    __syncthreads();        // every lane has read the old positions
+    s_pos[tid] = p;
+    __syncthreads();
+    // ---- reward: a good lane counts the adversaries that touch it; the world's count is a butterfly of integers
+    int mine = 0;
+    if (is_agent && !adversary) {
+        for (int j = 0; j < n_adv; ++j) {
+            const double2 o = s_pos[base + j];
+            const double dx = p.x - o.x, dy = p.y - o.y;
+            mine += sqrt(dx * dx + dy * dy) < kTagSize[1] + kTagSize[0];
+        }
+    }
+    int hits = mine;
+#pragma unroll
+    for (int stride = 1; stride < LPW; stride *= 2) hits += __shfl_xor(hits, stride);
+    // ---- outcome and restart (write_outcome with each agent's own reward, restart_from_fresh, store_world for one entity)
+    const bool done = t >= s.world_length, restart = done && s.auto_reset;
+    if (is_agent) {
+        const double pa = adversary ? kTagCatch * hits
+                                    : -kTagCatch * mine - (tag_bound(fabs(p.x)) + tag_bound(fabs(p.y)));
+        s.per_agent[ia] = pa;
+        s.rew[ia] = (float)pa;
+        s.done[ia] = done ? 1 : 0;
+        if (restart) {
+            p = reinterpret_cast<const double2*>(s.fresh_pos)[ia];
+            v = double2{0.0, 0.0};
+        }
+        reinterpret_cast<double2*>(s.pos)[ia] = p;
+        reinterpret_cast<double2*>(s.vel)[ia] = v;
+    }
+    if (is_land && restart) {
+        l = reinterpret_cast<const double2*>(s.fresh_land)[il];
+        l = double2{kTagLandmarkScale * l.x, kTagLandmarkScale * l.y};
+        reinterpret_cast<double2*>(s.land)[il] = l;
+    }
+    if (live && lane == 0) s.t[w] = restart ? 0 : t;
+    __syncthreads();        // every good lane has counted its adversaries
+    s_pos[tid] = p;
+    s_vel[tid] = v;
+    s_land[tid] = l;
+    __syncthreads();
+    // ---- observation of the (possibly restarted) world.  The row is n_adv segments of Pa pairs (x, y) and G of Pa - 1:
+    // vel_i, pos_i, the landmarks and the other agents relative to agent i, the velocities of the good agents other than
+    // i.  Flat pair q lies in segment q / Pa while q is among the adversaries', (q - n_adv Pa) / (Pa - 1) behind them
+    const int Pa = 2 + L + (A - 1) + G, adv_pairs = n_adv * Pa, pairs = live ? adv_pairs + G * (Pa - 1) : 0;
+    float2* row = reinterpret_cast<float2*>(s.obs) + w * (long long)(adv_pairs + G * (Pa - 1));
+    for (int q = lane; q < pairs; q += LPW) {
+        int i, f;
+        if (q < adv_pairs) {
+            i = q / Pa;
+            f = q - i * Pa;
+        } else {
+            const int g = (q - adv_pairs) / (Pa - 1);
+            i = n_adv + g;
+            f = q - adv_pairs - g * (Pa - 1);
+        }
+        const double2 me = s_pos[base + i];
+        double2 o;
+        if (f == 0) {
+            o = s_vel[base + i];
+        } else if (f == 1) {
+            o = me;
+        } else if (f < 2 + L) {
+            const double2 e = s_land[base + f - 2];
+            o = double2{e.x - me.x, e.y - me.y};
+        } else if (f < 2 + L + A - 1) {
+            int j = f - 2 - L;
+            j += j >= i;
+            const double2 e = s_pos[base + j];
+            o = double2{e.x - me.x, e.y - me.y};
+        } else {
+            int j = n_adv + f - (2 + L + A - 1);
+            j += i >= n_adv && j >= i;
+            o = s_vel[base + j];
+        }
+        row[q] = float2{(float)o.x, (float)o.y};
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // simple_world_comm (scenarios/simple_world_comm.py): simple_tag's adversaries and good agents among L obstacles that
 // collide, followed in the landmark list by 2 pieces of food and 2 forests that do not.  Agent 0, the adversaries' leader,
 // says one of 4 words per step (one word per world, advanced in place like simple_speaker_listener's; -1: nothing said
@@ -992,10 +1139,10 @@ extern "C" int mappo_simple_spread_step(double* pos, double* vel, double* landma
 }
 
 // LPW lanes per world, kWideThreads / LPW worlds per workgroup
-template <int LPW>
-int launch_wide(const Args& a, mappo_stream_t stream_) {
+template <int LPW, typename ArgsT>
+int launch_wide(void (*kernel)(ArgsT), const ArgsT& a, mappo_stream_t stream_) {
     constexpr int worlds = kWideThreads / LPW;
-    hipLaunchKernelGGL(spread_step_wide_kernel<LPW>, dim3((unsigned)((a.s.n + worlds - 1) / worlds)), dim3(kWideThreads), 0,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.s.n + worlds - 1) / worlds)), dim3(kWideThreads), 0,
                        static_cast<hipStream_t>(stream_), a);
     return (int)hipGetLastError();
 }
@@ -1013,7 +1160,8 @@ extern "C" int mappo_simple_spread_step_wide(double* pos, double* vel, double* l
                   n_worlds, world_length, auto_reset};
     const Args a{s, i64(actions), num_agents, num_landmarks};
     // two worlds to a wave where both entity counts fit half of one
-    return num_agents <= 32 && num_landmarks <= 32 ? launch_wide<32>(a, stream_) : launch_wide<64>(a, stream_);
+    return num_agents <= 32 && num_landmarks <= 32 ? launch_wide<32>(spread_step_wide_kernel<32>, a, stream_)
+                                                   : launch_wide<64>(spread_step_wide_kernel<64>, a, stream_);
 }
 
 extern "C" int mappo_simple_reference_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goals,
@@ -1076,6 +1224,24 @@ extern "C" int mappo_simple_tag_step(double* pos, double* vel, double* landmarks
     const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
                   n_worlds, world_length, auto_reset};
     return launch_step(tag_step_kernel, TagArgs{s, i64(actions), num_agents, num_adversaries, num_landmarks}, stream_);
+}
+
+extern "C" int mappo_simple_tag_step_wide(double* pos, double* vel, double* landmarks, int64_t* t,
+                                          const int64_t* actions, const double* fresh_pos,
+                                          const double* fresh_landmarks, float* obs, float* rewards, uint8_t* dones,
+                                          double* per_agent, int64_t n_worlds, int num_agents, int num_adversaries,
+                                          int num_landmarks, int world_length, int auto_reset, mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !actions || !obs || !rewards || !dones || !per_agent) return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || num_adversaries < 1 || num_adversaries >= num_agents || num_landmarks < 1 || world_length < 1)
+        return MAPPO_E_SHAPE;
+    if (num_agents > kWideMax || num_landmarks > kWideMax) return MAPPO_E_TOO_MANY;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    const TagArgs a{s, i64(actions), num_agents, num_adversaries, num_landmarks};
+    // two worlds to a wave where both entity counts fit half of one
+    return num_agents <= 32 && num_landmarks <= 32 ? launch_wide<32>(tag_step_wide_kernel<32>, a, stream_)
+                                                   : launch_wide<64>(tag_step_wide_kernel<64>, a, stream_);
 }
 
 extern "C" int mappo_simple_world_comm_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* comm,

@@ -24,6 +24,8 @@ agent ``-10`` per adversary touching it, minus ``bound(|x|) + bound(|y|)`` for l
 The scenario never sets ``world.world_length``, so the reference ends an episode after 25 steps (core.py:137) whatever
 ``--episode_length`` says; so do these worlds.
 """
+import os
+
 from onpolicy.envs.mpe.particle_worlds import TorchParticleWorlds
 from onpolicy.envs.spaces import Discrete
 
@@ -37,6 +39,7 @@ _MAX_SPEED = (1.0, 1.3)
 _CATCH = 10.0
 KERNEL_MAX_AGENTS = 16                  # MAPPO_ENV_MAX_ENTITIES
 KERNEL_MAX_LANDMARKS = 4                # MAPPO_TAG_MAX_LANDMARKS
+WIDE_MAX = 64                           # MAPPO_ENV_WIDE_MAX_ENTITIES
 
 
 def obs_widths(num_adversaries, num_good, num_landmarks):
@@ -53,16 +56,20 @@ class TorchSimpleTag(TorchParticleWorlds):
     one-hots, [N, A, 5] or concatenated [N, 5 A].  ``step`` returns obs [N, sum(obs_dims)] float32, rewards [N, A, 1]
     float32 (each agent's own), dones [N, A] bool, infos (lazy).  ``episode_length`` is accepted for the common call
     shape and unused: worlds report done at ``world_length`` steps (None: the reference's 25).  Kernel path:
-    ``mappo_simple_tag_step`` (K11 family), up to 16 agents and 4 landmarks; more take the tensor-op path."""
+    ``mappo_simple_tag_step`` (K11 family), up to 16 agents and 4 landmarks; more take the tensor-op path.  ``wide=True``
+    (None: ``MAPPO_TAG_WIDE=1`` in the environment when the worlds are built) opts into K11 wide
+    (``mappo_simple_tag_step_wide``: the lanes of a wave along a world's entities) for every shape up to 64 agents and 64
+    landmarks; worlds on the CPU step as tensor operations either way."""
     landmark_scale = 0.8
     shared_reward = False
 
     def __init__(self, n_threads, num_agents=4, num_landmarks=2, episode_length=25, seed=1, auto_reset=True,
-                 device="cpu", world_length=None, num_adversaries=3):
+                 device="cpu", world_length=None, num_adversaries=3, wide=None):
         a, l, adv = int(num_agents), int(num_landmarks), int(num_adversaries)
         assert 1 <= adv < a, "simple_tag: at least one adversary and one good agent (%d adversaries of %d agents)" % (adv, a)
         assert l >= 1, "simple_tag: at least one landmark"
         self.num_adversaries, self.num_good = adv, a - adv
+        self._wide = os.environ.get("MAPPO_TAG_WIDE") == "1" if wide is None else bool(wide)
         kind = [0] * adv + [1] * (a - adv)
         super().__init__(n_threads, a, l, _WORLD_LENGTH if world_length is None else world_length, seed, auto_reset,
                          device, obs_dim=obs_widths(adv, a - adv, l), action_space=lambda: Discrete(_MOVES),
@@ -86,6 +93,8 @@ class TorchSimpleTag(TorchParticleWorlds):
 
     @property
     def graph_safe(self):
+        if self._wide:
+            return self.device.type == "cuda" and max(self.a, self.l) <= WIDE_MAX
         return self.device.type == "cuda" and self.a <= KERNEL_MAX_AGENTS and self.l <= KERNEL_MAX_LANDMARKS
 
     def _obs(self):
@@ -132,7 +141,8 @@ class TorchSimpleTag(TorchParticleWorlds):
         from onpolicy import _native
         p = _native.ptr
         fresh_pos, fresh_land = fresh or (None, None)
-        _native.check(_native.lib().mappo_simple_tag_step(
+        name = "mappo_simple_tag_step_wide" if self._wide else "mappo_simple_tag_step"
+        _native.check(getattr(_native.lib(), name)(
             p(self.pos), p(self.vel), p(self.landmarks), p(self.t), p(idx), p(fresh_pos), p(fresh_land), p(obs),
             p(rewards), p(dones), p(per_agent), self.n, self.a, self.num_adversaries, self.l, self.world_length,
-            int(self.auto_reset), _native.stream_of(self.device)), "mappo_simple_tag_step")
+            int(self.auto_reset), _native.stream_of(self.device)), name)
