@@ -955,6 +955,24 @@ int mappo_simple_world_comm_step(double* pos, double* vel, double* landmarks, in
                                  int num_agents, int num_adversaries, int num_landmarks, int world_length,
                                  int auto_reset, mappo_stream_t stream);
 
+/* -------------------------------------------- K11 wide: simple_world_comm worlds of up to 64 entities ----
+ * The step of mappo_simple_world_comm_step -- its operands, its state updated in place, its outputs, its return codes --
+ * for A = num_agents in 2..MAPPO_ENV_WIDE_MAX_ENTITIES and L = num_landmarks, the obstacles, in
+ * 1..MAPPO_ENV_WIDE_MAX_ENTITIES - 4: food and forests take landmark lanes too.  The lanes of a wave lie along a world's
+ * entities (32 lanes per world while A, L + 4 <= 32, else 64) and the world's image in LDS, as in
+ * mappo_simple_tag_step_wide.  Every agent lane finds its own nearest good agent or food and decides whether it is
+ * inside each forest; the world's two forest masks are wave ballots, 64 bits wide, and who sees whom is the thin
+ * kernel's rule on them.  The leader's word is read by every lane of its world and stored by lane 0.  The observation
+ * row, whose adversary and good-agent segments differ in width and in field order, leaves as 8-byte stores that the
+ * world's lanes lay side by side along the whole row.  The arithmetic is the thin kernel's in its order; what crosses
+ * lanes is an integer count, minima and bit masks, so no floating sum is reordered against it.  MAPPO_E_SHAPE for Nadv
+ * outside 1..A-1 or L < 1, MAPPO_E_TOO_MANY for A > 64 or L + 4 > 64; nothing is launched or written then. */
+int mappo_simple_world_comm_step_wide(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* comm,
+                                      const int64_t* actions, const double* fresh_pos, const double* fresh_landmarks,
+                                      float* obs, float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
+                                      int num_agents, int num_adversaries, int num_landmarks, int world_length,
+                                      int auto_reset, mappo_stream_t stream);
+
 /* ------------------------------------------------------------------- K16: Hanabi tables on the device ----
  * The batched Hanabi stepper of include/hanabi_batch.h (libhanabi_batch.so, host) with its tables in device memory: the
  * same rules, deal and encoder source (csrc/hanabi_rules.h), so for equal seeds and moves every row, reward, status and

@@ -1112,6 +1112,216 @@ __global__ void __launch_bounds__(64) world_comm_step_kernel(WorldCommArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// simple_world_comm past kMax agents or kWcObstacles obstacles (K11 wide for simple_world_comm): tag_step_wide_kernel's
+// work split -- LPW lanes own a world, lane e its agent e and its landmark e (obstacles, food and forests: all L + 4 have
+// a lane), the world's image in LDS, pair loops over the runtime counts -- with world_comm_step_kernel's arithmetic,
+// expression by expression and in its order.  What crosses lanes here, beyond the catch count:
+//   - the nearest good agent of an adversary and the nearest food of a good agent: each lane's own loop over the world's
+//     image, and a minimum is exact in any order;
+//   - who is inside which forest: each agent lane decides for itself, and the world's two masks are wave ballots (the
+//     world's half of one where a wave holds two worlds), 64-bit so that agent 63 has a bit: no LDS round trip, and "i
+//     sees j" stays the thin kernel's expression on masks;
+//   - the leader's word: every lane of the world reads it from the actions, lane 0 stores it.
+// No floating sum runs in another order than the thin kernel's.  The observation is ONE row per world whose two kinds
+// of segment differ in width (an adversary's is 3 pairs longer) and in field order (an adversary: the good agents'
+// velocities, its flags, the word; a good agent: its flags, the other good agents' velocities); the world's lanes walk the
+// concatenated row as tag_step_wide_kernel's do, one integer division per pair.
+template <int LPW>
+__global__ void __launch_bounds__(kWideThreads) world_comm_step_wide_kernel(WorldCommArgs a) {
+    static_assert(LPW == 32 || LPW == 64, "a world is half a wave or a whole one");
+    // one double2 per lane and array: the image of world slot k is [k * LPW, (k + 1) * LPW)
+    __shared__ double2 s_pos[kWideThreads], s_vel[kWideThreads], s_land[kWideThreads];
+    const World& s = a.s;
+    const int A = a.A, L = a.L, n_adv = a.n_adv, G = A - n_adv, Lt = a.L + kWcFixed;
+    const int tid = threadIdx.x, lane = tid % LPW, base = tid - lane;
+    const long long w = (long long)blockIdx.x * (kWideThreads / LPW) + tid / LPW;
+    // no thread leaves before the last barrier: a world past n, and a lane past the world's entities, is predicated
+    const bool live = w < s.n, is_agent = live && lane < A, is_land = live && lane < Lt, adversary = lane < n_adv;
+    const long long ia = w * A + lane, il = w * Lt + lane;
+    const double radius = adversary ? kWcSize[0] : kWcSize[1];
+    double2 p = {0.0, 0.0}, v = {0.0, 0.0}, l = {0.0, 0.0};
+    long long mv = 0, t = 0;
+    int word = -1;
+    if (is_agent) {
+        p = reinterpret_cast<const double2*>(s.pos)[ia];
+        v = reinterpret_cast<const double2*>(s.vel)[ia];
+        mv = a.act[w * (A + 1) + (lane == 0 ? 0 : lane + 1)];
+    }
+    if (is_land) l = reinterpret_cast<const double2*>(s.land)[il];
+    if (live) {
+        t = s.t[w] + 1;
+        word = (int)a.act[w * (A + 1) + 1];     // the word becomes the communication state
+    }
+    s_pos[tid] = p;
+    s_land[tid] = l;
+    __syncthreads();
+    // ---- forces: action (accel^2) + soft contacts with the agents, then with the obstacles, the first L landmarks
+    // (add_contact_forces and add_landmark_contact_forces for one agent), then integrate<true>'s expressions
+    if (is_agent) {
+        const ByKind size{n_adv, kWcSize[0], kWcSize[1]};
+        const double accel = adversary ? kWcAccel[0] : kWcAccel[1];
+        double fx, fy, sx = 0.0, sy = 0.0;
+        action_force(mv, fx, fy, accel * accel);
+        for (int j = 0; j < A; ++j) {
+            if (j == lane) continue;
+            const double2 o = s_pos[base + j];
+            contact_force(p.x - o.x, p.y - o.y, radius + size.of(j), sx, sy);
+        }
+        fx += sx;
+        fy += sy;
+        sx = sy = 0.0;
+        for (int k = 0; k < L; ++k) {
+            const double2 o = s_land[base + k];
+            contact_force(p.x - o.x, p.y - o.y, radius + kWcObstacleSize, sx, sy);
+        }
+        fx += sx;
+        fy += sy;
+        v.x = v.x * (1 - kDamping) + fx * kDt;
+        v.y = v.y * (1 - kDamping) + fy * kDt;
+        const double speed = sqrt(v.x * v.x + v.y * v.y), top = adversary ? kWcMaxSpeed[0] : kWcMaxSpeed[1];
+        if (speed > top) {
+            v.x = v.x / speed * top;
+            v.y = v.y / speed * top;
+        }
+        p.x = p.x + v.x * kDt;
+        p.y = p.y + v.y * kDt;
+    }
+    __syncthreads();        // every lane has read the old positions
+    s_pos[tid] = p;
+    __syncthreads();
+    // ---- reward.  An adversary lane: its distance to the nearest good agent.  A good lane: the adversaries that touch
+    // it, the food it touches and its distance to the nearest food.  The world's catch count is a butterfly of integers
+    int mine = 0, fed = 0;
+    double nearest = 1e300;
+    if (is_agent && adversary) {
+        for (int g = n_adv; g < A; ++g) {
+            const double2 o = s_pos[base + g];
+            const double dx = o.x - p.x, dy = o.y - p.y;
+            nearest = fmin(nearest, sqrt(dx * dx + dy * dy));
+        }
+    }
+    if (is_agent && !adversary) {
+        for (int j = 0; j < n_adv; ++j) {
+            const double2 o = s_pos[base + j];
+            const double dx = p.x - o.x, dy = p.y - o.y;
+            mine += sqrt(dx * dx + dy * dy) < kWcSize[1] + kWcSize[0];
+        }
+        for (int f = 0; f < kWcFood; ++f) {
+            const double2 o = s_land[base + L + f];
+            const double dx = p.x - o.x, dy = p.y - o.y;
+            const double d = sqrt(dx * dx + dy * dy);
+            fed += d < kWcSize[1] + kWcFoodSize;
+            nearest = fmin(nearest, d);
+        }
+    }
+    int hits = mine;
+#pragma unroll
+    for (int stride = 1; stride < LPW; stride *= 2) hits += __shfl_xor(hits, stride);
+    // ---- outcome and restart (write_outcome with each agent's own reward, restart_from_fresh, store_world for one
+    // entity); after a restart nothing has been said
+    const bool done = t >= s.world_length, restart = done && s.auto_reset;
+    if (is_agent) {
+        double pa = -kWcCatch * mine;
+        if (adversary) {
+            pa = -0.1 * nearest;
+            pa += kWcCatch * hits;
+        } else {
+            pa = pa - 2 * (tag_bound(fabs(p.x)) + tag_bound(fabs(p.y))) + kWcFoodReward * fed + 0.05 * nearest;
+        }
+        s.per_agent[ia] = pa;
+        s.rew[ia] = (float)pa;
+        s.done[ia] = done ? 1 : 0;
+        if (restart) {
+            p = reinterpret_cast<const double2*>(s.fresh_pos)[ia];
+            v = double2{0.0, 0.0};
+        }
+        reinterpret_cast<double2*>(s.pos)[ia] = p;
+        reinterpret_cast<double2*>(s.vel)[ia] = v;
+    }
+    if (is_land && restart) {
+        l = reinterpret_cast<const double2*>(s.fresh_land)[il];
+        l = double2{kWcLandmarkScale * l.x, kWcLandmarkScale * l.y};
+        reinterpret_cast<double2*>(s.land)[il] = l;
+    }
+    if (restart) word = -1;
+    if (live && lane == 0) {
+        s.t[w] = restart ? 0 : t;
+        a.comm[w] = word;
+    }
+    __syncthreads();        // every lane has measured its distances
+    s_pos[tid] = p;
+    s_vel[tid] = v;
+    s_land[tid] = l;
+    __syncthreads();
+    // ---- who is inside which forest of the (possibly restarted) world: lane i decides for agent i, idle lanes vote no,
+    // and bit i of the world's masks in0 / in1 is agent i's answer
+    bool flag0 = false, flag1 = false;
+    if (is_agent) {
+        const double2 f0 = s_land[base + L + kWcFood], f1 = s_land[base + L + kWcFood + 1];
+        const double reach = radius + kWcForestSize;
+        const double ax = p.x - f0.x, ay = p.y - f0.y, bx = p.x - f1.x, by = p.y - f1.y;
+        flag0 = sqrt(ax * ax + ay * ay) < reach;
+        flag1 = sqrt(bx * bx + by * by) < reach;
+    }
+    unsigned long long in0 = __ballot(flag0), in1 = __ballot(flag1);
+    if (LPW == 32) {        // the world's own half of the wave
+        in0 = (in0 >> (tid & 32)) & 0xffffffffull;
+        in1 = (in1 >> (tid & 32)) & 0xffffffffull;
+    }
+    const unsigned long long open = ~(in0 | in1);
+    // ---- observation.  The row is n_adv segments of Pa pairs (x, y) and G of Pa - 3.  Both begin with C pairs: vel_i,
+    // pos_i, the landmarks and the other agents relative to agent i, (0, 0) for one it does not see.  An adversary goes on
+    // with the G good agents' velocities (masked alike), its flag pair and the word's one-hot as two pairs; a good agent
+    // with its flag pair and the G - 1 other good agents' velocities (masked).  Flat pair q lies in segment q / Pa while
+    // q is among the adversaries', (q - n_adv Pa) / (Pa - 3) behind them
+    const int C = 2 + Lt + (A - 1), Pa = C + G + 3, Pg = Pa - 3;
+    const int adv_pairs = n_adv * Pa, pairs = live ? adv_pairs + G * Pg : 0;
+    float2* row = reinterpret_cast<float2*>(s.obs) + w * (long long)(adv_pairs + G * Pg);
+    for (int q = lane; q < pairs; q += LPW) {
+        int i, f;
+        if (q < adv_pairs) {
+            i = q / Pa;
+            f = q - i * Pa;
+        } else {
+            const int g = (q - adv_pairs) / Pg;
+            i = n_adv + g;
+            f = q - adv_pairs - g * Pg;
+        }
+        const bool i0 = (in0 >> i) & 1ull, i1 = (in1 >> i) & 1ull;
+        // bit j: agent i sees agent j
+        const unsigned long long sees = i == 0 ? ~0ull : (i0 ? in0 : 0ull) | (i1 ? in1 : 0ull) | (i0 || i1 ? 0ull : open);
+        const double2 me = s_pos[base + i];
+        double2 o = {0.0, 0.0};
+        int j = -1;                 // >= 0: the good agent whose velocity, where agent i sees it, is this pair
+        if (f == 0) {
+            o = s_vel[base + i];
+        } else if (f == 1) {
+            o = me;
+        } else if (f < 2 + Lt) {
+            const double2 e = s_land[base + f - 2];
+            o = double2{e.x - me.x, e.y - me.y};
+        } else if (f < C) {
+            int k = f - 2 - Lt;
+            k += k >= i;
+            const double2 e = s_pos[base + k];
+            if ((sees >> k) & 1ull) o = double2{e.x - me.x, e.y - me.y};
+        } else if (i < n_adv) {
+            if (f < C + G) j = n_adv + f - C;
+            else if (f == C + G) o = double2{i0 ? 1.0 : -1.0, i1 ? 1.0 : -1.0};
+            else if (f == C + G + 1) o = double2{word == 0 ? 1.0 : 0.0, word == 1 ? 1.0 : 0.0};
+            else o = double2{word == 2 ? 1.0 : 0.0, word == 3 ? 1.0 : 0.0};
+        } else if (f == C) {
+            o = double2{i0 ? 1.0 : -1.0, i1 ? 1.0 : -1.0};
+        } else {
+            j = n_adv + f - C - 1;
+            j += j >= i;
+        }
+        if (j >= 0 && ((sees >> j) & 1ull)) o = s_vel[base + j];
+        row[q] = float2{(float)o.x, (float)o.y};
+    }
+}
+
 // one thread per world, 64 to a block
 template <typename ArgsT>
 int launch_step(void (*kernel)(ArgsT), const ArgsT& a, mappo_stream_t stream_) {
@@ -1260,4 +1470,26 @@ extern "C" int mappo_simple_world_comm_step(double* pos, double* vel, double* la
                   n_worlds, world_length, auto_reset};
     return launch_step(world_comm_step_kernel,
                        WorldCommArgs{s, i64(comm), i64(actions), num_agents, num_adversaries, num_landmarks}, stream_);
+}
+
+extern "C" int mappo_simple_world_comm_step_wide(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* comm,
+                                                 const int64_t* actions, const double* fresh_pos,
+                                                 const double* fresh_landmarks, float* obs, float* rewards,
+                                                 uint8_t* dones, double* per_agent, int64_t n_worlds, int num_agents,
+                                                 int num_adversaries, int num_landmarks, int world_length,
+                                                 int auto_reset, mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !comm || !actions || !obs || !rewards || !dones || !per_agent)
+        return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || num_adversaries < 1 || num_adversaries >= num_agents || num_landmarks < 1 || world_length < 1)
+        return MAPPO_E_SHAPE;
+    // food and forests have lanes of their own
+    if (num_agents > kWideMax || num_landmarks > kWideMax - kWcFixed) return MAPPO_E_TOO_MANY;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    const WorldCommArgs a{s, i64(comm), i64(actions), num_agents, num_adversaries, num_landmarks};
+    // two worlds to a wave where the agents and all the landmarks fit half of one
+    return num_agents <= 32 && num_landmarks + kWcFixed <= 32
+               ? launch_wide<32>(world_comm_step_wide_kernel<32>, a, stream_)
+               : launch_wide<64>(world_comm_step_wide_kernel<64>, a, stream_);
 }

@@ -34,6 +34,8 @@ reference -- ``+0.05`` times its distance to the nearest food.
 The scenario never sets ``world.world_length``, so the reference ends an episode after 25 steps (core.py:137) whatever
 ``--episode_length`` says; so do these worlds.
 """
+import os
+
 from onpolicy.envs.mpe.particle_worlds import TorchParticleWorlds
 from onpolicy.envs.spaces import Discrete
 from onpolicy.utils.multi_discrete import MultiDiscrete
@@ -52,6 +54,7 @@ _CATCH = 5.0
 _FOOD_REWARD = 2.0
 KERNEL_MAX_AGENTS = 16                  # MAPPO_ENV_MAX_ENTITIES
 KERNEL_MAX_LANDMARKS = 4                # MAPPO_WORLD_COMM_MAX_OBSTACLES: obstacles; food and forests come on top
+WIDE_MAX = 64                           # MAPPO_ENV_WIDE_MAX_ENTITIES: agents; obstacles, food and forests together
 
 
 def obs_widths(num_adversaries, num_good, num_landmarks):
@@ -71,18 +74,22 @@ class TorchSimpleWorldComm(TorchParticleWorlds):
     [N, sum(obs_dims)] float32, rewards [N, A, 1] float32 (each agent's own), dones [N, A] bool, infos (lazy).
     ``episode_length`` is accepted for the common call shape and unused: worlds report done at ``world_length`` steps
     (None: the reference's 25).  Kernel path: ``mappo_simple_world_comm_step`` (K11 family), up to 16 agents and 4
-    obstacles; more take the tensor-op path."""
+    obstacles; more take the tensor-op path.  ``wide=True`` (None: ``MAPPO_WORLD_COMM_WIDE=1`` in the environment when
+    the worlds are built) opts into K11 wide (``mappo_simple_world_comm_step_wide``: the lanes of a wave along a world's
+    entities) for every shape up to 64 agents and 60 obstacles; worlds on the CPU step as tensor operations either
+    way."""
     state_names = TorchParticleWorlds.state_names + ("comm",)
     landmark_scale = 0.8
     shared_reward = False
 
     def __init__(self, n_threads, num_agents=6, num_landmarks=1, episode_length=25, seed=1, auto_reset=True,
-                 device="cpu", world_length=None, num_adversaries=4):
+                 device="cpu", world_length=None, num_adversaries=4, wide=None):
         a, obstacles, adv = int(num_agents), int(num_landmarks), int(num_adversaries)
         assert 1 <= adv < a, ("simple_world_comm: at least one adversary and one good agent (%d adversaries of %d agents)"
                               % (adv, a))
         assert obstacles >= 1, "simple_world_comm: at least one landmark"
         self.num_adversaries, self.num_good, self.num_obstacles = adv, a - adv, obstacles
+        self._wide = os.environ.get("MAPPO_WORLD_COMM_WIDE") == "1" if wide is None else bool(wide)
         kind = [0] * adv + [1] * (a - adv)
         spaces = [MultiDiscrete([[0, _MOVES - 1], [0, _WORDS - 1]])] + [Discrete(_MOVES) for _ in range(a - 1)]
         super().__init__(n_threads, a, obstacles + _FIXED, _WORLD_LENGTH if world_length is None else world_length, seed,
@@ -114,6 +121,8 @@ class TorchSimpleWorldComm(TorchParticleWorlds):
 
     @property
     def graph_safe(self):
+        if self._wide:
+            return self.device.type == "cuda" and max(self.a, self.l) <= WIDE_MAX
         return (self.device.type == "cuda" and self.a <= KERNEL_MAX_AGENTS
                 and self.num_obstacles <= KERNEL_MAX_LANDMARKS)
 
@@ -203,7 +212,8 @@ class TorchSimpleWorldComm(TorchParticleWorlds):
         from onpolicy import _native
         p = _native.ptr
         fresh_pos, fresh_land = fresh or (None, None)
-        _native.check(_native.lib().mappo_simple_world_comm_step(
+        name = "mappo_simple_world_comm_step_wide" if self._wide else "mappo_simple_world_comm_step"
+        _native.check(getattr(_native.lib(), name)(
             p(self.pos), p(self.vel), p(self.landmarks), p(self.t), p(self.comm), p(idx), p(fresh_pos), p(fresh_land),
             p(obs), p(rewards), p(dones), p(per_agent), self.n, self.a, self.num_adversaries, self.num_obstacles,
-            self.world_length, int(self.auto_reset), _native.stream_of(self.device)), "mappo_simple_world_comm_step")
+            self.world_length, int(self.auto_reset), _native.stream_of(self.device)), name)

@@ -3,13 +3,14 @@
 -- or, with ``--scenario simple_tag --num_adversaries V``, simple_tag worlds through ``mappo_simple_tag_step`` (through
 ``mappo_simple_tag_step_wide``, up to 64 agents and landmarks, with ``MAPPO_TAG_WIDE=1`` in the environment), or, with
 ``--scenario simple_world_comm --num_adversaries V``, simple_world_comm worlds (``--num_landmarks`` obstacles) through
-``mappo_simple_world_comm_step``, or, with ``--scenario simple_spread``, simple_spread worlds through
+``mappo_simple_world_comm_step`` (through ``mappo_simple_world_comm_step_wide``, up to 64 agents and 60 obstacles, with
+``MAPPO_WORLD_COMM_WIDE=1`` in the environment), or, with ``--scenario simple_spread``, simple_spread worlds through
 ``mappo_simple_spread_step`` up to 16 agents and landmarks and ``mappo_simple_spread_step_wide`` past that (and for every
 shape up to 64 with ``MAPPO_SPREAD_WIDE=1`` in the environment) -- and nothing else, for a kernel-trace run of its own:
 
     rocprofv3 --kernel-trace --stats -f csv -d out -o push -- python tools/push_step_trace.py --worlds 4096
 
-The trace's ``push_step_kernel`` (``tag_step_kernel``, ``world_comm_step_kernel``, ``spread_step_kernel``, ``spread_step_wide_kernel<32 | 64>``, ``tag_step_wide_kernel<32 | 64>``) row is the step kernel's own time at that number of worlds (the generator draws of a
+The trace's ``push_step_kernel`` (``tag_step_kernel``, ``world_comm_step_kernel``, ``spread_step_kernel``, ``spread_step_wide_kernel<32 | 64>``, ``tag_step_wide_kernel<32 | 64>``, ``world_comm_step_wide_kernel<32 | 64>``) row is the step kernel's own time at that number of worlds (the generator draws of a
 step and the action tensor are separate kernels in the same trace).  Prints one JSON line with the shape and the wall
 time per step as the host sees it.
 """
