@@ -880,6 +880,33 @@ int mappo_simple_push_step(double* pos, double* vel, double* landmarks, int64_t*
                            int64_t n_worlds, int num_agents, int num_landmarks, int world_length, int auto_reset,
                            mappo_stream_t stream);
 
+/* ----------------------------------------------------- K11 family: simple_adversary worlds on the device ----
+ * One env step of `n_worlds` physical-deception worlds (reference onpolicy/envs/mpe/scenarios/simple_adversary.py,
+ * environment.py:115-255, core.py:160-190 and :207-288; A = num_agents in 2..MAPPO_ENV_WIDE_MAX_ENTITIES, L =
+ * num_landmarks in 1..MAPPO_ENV_WIDE_MAX_ENTITIES, independently of A: the reference's scenario builds A - 1) as one
+ * launch.  Agent 0 is the adversary, agents 1..A-1 are good; all move and are silent, and nothing collides: the force on
+ * an agent is its action's alone (sensitivity 5, damping 0.25, dt 0.1, no top speed).  State is updated in place: pos /
+ * vel [n, A, 2] and landmarks [n, L, 2] float64, t [n] int64, goal [n] int64 (the goal landmark all agents share,
+ * 0..L-1).  actions [n, A] int64 in 0..4.  Worlds whose t reaches world_length report done and (auto_reset) restart from
+ * fresh_pos [n, A, 2], fresh_landmarks [n, L, 2] (uniform(-1, 1) draws, the landmarks NOT scaled) and fresh_goal [n], at
+ * rest.  Outputs: obs [n, Da + (A - 1) Dg] float32, one row per world that is also the centralised observation: columns
+ * 0:Da the adversary's observation (landmarks and other agents relative to it; Da = 2 L + 2 (A - 1)), then Dg = 2 + Da
+ * columns per good agent in agent order (the goal relative to it, landmarks relative to it, other agents relative to it);
+ * no velocities, no colours.  obs is written after a restart, so a restarted world reports its fresh state; rewards, dones
+ * and per_agent are those of the step that ended the episode.  The world is not collaborative: rewards [n, A, 1] float32
+ * and per_agent [n, A] float64 (the individual_reward info) both hold each agent's own reward, with d_i = |pos_i - goal|
+ * -d_0^2 for the adversary and d_0 - min over good agents d_g for every good agent; dones [n, A] bytes.
+ * One kernel for every shape: the lanes of a wave lie along a world's entities (32 lanes per world while A, L <= 32, else
+ * 64), each keeps its agent and its landmark in registers, the goal's position and d_0 travel by shuffles and the minimum
+ * is an fmin butterfly, so no floating sum is reordered against the tensor step; the row leaves as 8-byte stores that the
+ * world's lanes lay side by side (obs must be 8-byte aligned).  MAPPO_E_SHAPE for A < 2 or L < 1, MAPPO_E_TOO_MANY for
+ * A > 64 or L > 64; nothing is launched or written then. */
+int mappo_simple_adversary_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,
+                                const int64_t* actions, const double* fresh_pos, const double* fresh_landmarks,
+                                const int64_t* fresh_goal, float* obs, float* rewards, uint8_t* dones,
+                                double* per_agent, int64_t n_worlds, int num_agents, int num_landmarks,
+                                int world_length, int auto_reset, mappo_stream_t stream);
+
 /* ----------------------------------------------------------- K11 family: simple_tag worlds on the device ----
  * One env step of `n_worlds` predator-prey worlds (reference onpolicy/envs/mpe/scenarios/simple_tag.py:6-144,
  * environment.py:115-255, core.py:207-321: action force, integration with a top speed, contact forces; A = num_agents in

@@ -675,6 +675,131 @@ __global__ void __launch_bounds__(64) push_step_kernel(PushArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// simple_adversary (physical deception; scenarios/simple_adversary.py): agent 0, the adversary, has to find the goal
+// landmark among L that the good agents 1..A-1 know and cover.  Nothing collides and nobody speaks, so the physics is the
+// action force and the integration alone; one goal per world, advanced in place like simple_push's.  Not collaborative:
+// the adversary is paid -d_0^2 and every good agent d_0 - min over good agents d_g, with d_i = |pos_i - goal|.  The
+// observation holds positions only (no velocity, no colours) and leaves as ONE row per world, the adversary's columns
+// first: the landmarks and the other agents relative to it; a good agent's segment has the goal relative to it in front.
+//
+// One kernel for every shape from 2 to kWideMax agents, on the wide kernels' work split (LPW lanes own a world, lane e
+// its agent e and its landmark e) but not their design: with no pair loop the step is a row writer -- (2 A + L) x 16
+// bytes read, Da + (A - 1) Dg floats written per world, 65 KB of them at A = 64 -- with a little arithmetic in front.
+// That arithmetic never leaves the registers: force and integration are the lane's own, the goal's position comes by
+// a shuffle from lane `goal`, d_0 by a shuffle from lane 0, and the minimum is an fmin butterfly over the world's lanes to
+// which the adversary, idle lanes and dead worlds contribute +inf.  A minimum does not depend on its order and the
+// adversary's reward has one addend, so no floating sum is reordered against the tensor step.  LDS is written once, with
+// the (possibly restarted) positions and landmarks, for the row: no earlier read of it, so one barrier publishes it.
+struct AdversaryArgs {
+    World s;                        // s.obs: [N, (2 L + 2 (A - 1)) + (A - 1) (2 + 2 L + 2 (A - 1))]
+    long long* goal;                // [N] goal landmark, 0..L-1
+    const long long* act;           // [N, A] action indices 0..4
+    const long long* fresh_goal;    // [N] 0..L-1
+    int A, L;
+};
+
+// the smallest x over the LPW lanes of a world, in every one of them
+template <int LPW>
+__device__ __forceinline__ double world_min(double x) {
+#pragma unroll
+    for (int stride = 1; stride < LPW; stride *= 2) x = fmin(x, __shfl_xor(x, stride));
+    return x;
+}
+
+template <int LPW>
+__global__ void __launch_bounds__(kWideThreads) adversary_step_kernel(AdversaryArgs a) {
+    static_assert(LPW == 32 || LPW == 64, "a world is half a wave or a whole one");
+    // one double2 per lane and array: the image of world slot k is [k * LPW, (k + 1) * LPW)
+    __shared__ double2 s_pos[kWideThreads], s_land[kWideThreads];
+    const World& s = a.s;
+    const int A = a.A, L = a.L;
+    const int tid = threadIdx.x, lane = tid % LPW, base = tid - lane;
+    const long long w = (long long)blockIdx.x * (kWideThreads / LPW) + tid / LPW;
+    // no thread leaves before the barrier: a world past n, and a lane past the world's entities, is predicated
+    const bool live = w < s.n, is_agent = live && lane < A, is_land = live && lane < L;
+    const long long ia = w * A + lane, il = w * L + lane;
+    double2 p = {0.0, 0.0}, v = {0.0, 0.0}, l = {0.0, 0.0};
+    long long mv = 0, t = 0;
+    int goal = 0;
+    if (is_agent) {
+        p = reinterpret_cast<const double2*>(s.pos)[ia];
+        v = reinterpret_cast<const double2*>(s.vel)[ia];
+        mv = a.act[ia];
+    }
+    if (is_land) l = reinterpret_cast<const double2*>(s.land)[il];
+    if (live) {
+        t = s.t[w] + 1;
+        goal = (int)a.goal[w];
+    }
+    // ---- forces: the action alone, then integrate's expressions
+    if (is_agent) {
+        double fx, fy;
+        action_force(mv, fx, fy);
+        v.x = v.x * (1 - kDamping) + fx * kDt;
+        v.y = v.y * (1 - kDamping) + fy * kDt;
+        p.x = p.x + v.x * kDt;
+        p.y = p.y + v.y * kDt;
+    }
+    // ---- reward (simple_adversary.py:78-111): every lane its distance to the goal, whose position lane `goal` holds
+    const double gx = __shfl(l.x, goal, LPW), gy = __shfl(l.y, goal, LPW);
+    const double dx = p.x - gx, dy = p.y - gy;
+    const double d2 = dx * dx + dy * dy, d = sqrt(d2);
+    const double own = __shfl(d, 0, LPW);                                          // the adversary's
+    const double nearest = world_min<LPW>(is_agent && lane > 0 ? d : HUGE_VAL);
+    // ---- outcome and restart (write_outcome with each agent's own reward, restart_from_fresh, store_world for one entity)
+    const bool done = t >= s.world_length, restart = done && s.auto_reset;
+    if (is_agent) {
+        const double pa = lane == 0 ? -d2 : own - nearest;
+        s.per_agent[ia] = pa;
+        s.rew[ia] = (float)pa;
+        s.done[ia] = done ? 1 : 0;
+        if (restart) {
+            p = reinterpret_cast<const double2*>(s.fresh_pos)[ia];
+            v = double2{0.0, 0.0};
+        }
+        reinterpret_cast<double2*>(s.pos)[ia] = p;
+        reinterpret_cast<double2*>(s.vel)[ia] = v;
+    }
+    if (is_land && restart) {
+        l = reinterpret_cast<const double2*>(s.fresh_land)[il];        // (no landmark scale in this scenario)
+        reinterpret_cast<double2*>(s.land)[il] = l;
+    }
+    if (live && restart) goal = (int)a.fresh_goal[w];
+    if (live && lane == 0) {
+        s.t[w] = restart ? 0 : t;
+        if (restart) a.goal[w] = goal;
+    }
+    s_pos[tid] = p;
+    s_land[tid] = l;
+    __syncthreads();
+    // ---- observation of the (possibly restarted) world (simple_adversary.py:119-137).  The row is one segment of Pa
+    // pairs (x, y), the adversary's, and A - 1 of Pa + 1.  With a good agent's fields numbered from 0, the goal, and the
+    // adversary's from 1, field f is landmark f - 1 up to L and an other agent from there on.  The world's lanes walk
+    // the concatenated row: lane k writes its pairs k, k + LPW, ..., one integer division a pair behind the first segment
+    const int Pa = L + A - 1, pairs = live ? Pa + (A - 1) * (Pa + 1) : 0;
+    float2* row = reinterpret_cast<float2*>(s.obs) + w * (long long)(Pa + (A - 1) * (Pa + 1));
+    const double2 target = s_land[base + goal];
+    for (int q = lane; q < pairs; q += LPW) {
+        int i = 0, f = q + 1;
+        if (q >= Pa) {
+            const int g = (q - Pa) / (Pa + 1);
+            i = 1 + g;
+            f = q - Pa - g * (Pa + 1);
+        }
+        const double2 me = s_pos[base + i];
+        double2 e = target;
+        if (f > L) {
+            int j = f - 1 - L;
+            j += j >= i;
+            e = s_pos[base + j];
+        } else if (f > 0) {
+            e = s_land[base + f - 1];
+        }
+        row[q] = float2{(float)(e.x - me.x), (float)(e.y - me.y)};
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // simple_tag (predator-prey; scenarios/simple_tag.py): agents 0..Nadv-1, the adversaries, chase the good agents Nadv..A-1
 // among landmarks that collide and never move.  An adversary is large and slow, a good agent small and fast; every agent
 // moves, is silent, collides and has a top speed.  Not collaborative: each agent is paid its own reward.  No state besides
@@ -1419,6 +1544,25 @@ extern "C" int mappo_simple_push_step(double* pos, double* vel, double* landmark
                   n_worlds, world_length, auto_reset};
     return launch_step(push_step_kernel, PushArgs{s, i64(goal), i64(actions), i64(fresh_goal), num_agents, num_landmarks},
                        stream_);
+}
+
+extern "C" int mappo_simple_adversary_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,
+                                           const int64_t* actions, const double* fresh_pos,
+                                           const double* fresh_landmarks, const int64_t* fresh_goal, float* obs,
+                                           float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
+                                           int num_agents, int num_landmarks, int world_length, int auto_reset,
+                                           mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !goal || !actions || !obs || !rewards || !dones || !per_agent)
+        return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks || !fresh_goal)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || num_agents < 2 || num_landmarks < 1 || world_length < 1) return MAPPO_E_SHAPE;
+    if (num_agents > kWideMax || num_landmarks > kWideMax) return MAPPO_E_TOO_MANY;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    const AdversaryArgs a{s, i64(goal), i64(actions), i64(fresh_goal), num_agents, num_landmarks};
+    // two worlds to a wave where both entity counts fit half of one
+    return num_agents <= 32 && num_landmarks <= 32 ? launch_wide<32>(adversary_step_kernel<32>, a, stream_)
+                                                   : launch_wide<64>(adversary_step_kernel<64>, a, stream_);
 }
 
 extern "C" int mappo_simple_tag_step(double* pos, double* vel, double* landmarks, int64_t* t, const int64_t* actions,

@@ -14,8 +14,10 @@ own, 1 or 2 landmarks; the separated runner only, like simple_speaker_listener) 
 runner only) and simple_world_comm (envs/mpe/simple_world_comm.py: simple_tag's two kinds of agent among
 ``--num_landmarks`` obstacles, two pieces of food and two forests that hide agents, the first adversary a leader with a
 MultiDiscrete action that says a word per step; 4 adversaries and 2 good agents where the two flags are not given; the
-separated runner only); every other case -- simple_reference, simple_speaker_listener, simple_push, simple_tag or
-simple_world_comm without the flag, any other scenario, and the eval envs of ``--use_eval`` in every case but one -- is built per worker from an external env tree (MAPPO_ENVS_PATH).  The exception:
+separated runner only) and simple_adversary (envs/mpe/simple_adversary.py: one adversary and num_agents - 1 good agents
+among num_agents - 1 landmarks whatever ``--num_landmarks`` says, as in the reference; the separated runner only, and a HIP device only: its step has no tensor-op route in a run); every
+other case -- simple_reference, simple_speaker_listener, simple_push, simple_tag, simple_world_comm or simple_adversary
+without the flag, any other scenario, and the eval envs of ``--use_eval`` in every case but one -- is built per worker from an external env tree (MAPPO_ENVS_PATH).  The exception:
 ``--use_device_eval`` (with ``--use_eval --use_device_env``, rmappo / mappo / ippo) builds the eval worlds of the
 device scenarios in-tree on the device too, and ``eval()`` then runs on tensors, its step as one captured graph launch
 (runner/shared/eval_graph.py).  wandb / setproctitle are optional.
@@ -46,11 +48,16 @@ Predator-prey with forests, food and a speaking leader on the device, four adver
         --num_agents 6 --num_adversaries 4 --num_good_agents 2 --num_landmarks 1 --n_rollout_threads 128 \
         --num_mini_batch 1 --episode_length 25 --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 \
         --critic_lr 7e-4 --share_policy --use_device_env
+Physical deception on the device, one adversary against two good agents among two landmarks (25-step episodes as well):
+    python -m onpolicy.scripts.train.train_mpe --env_name MPE --algorithm_name rmappo --scenario_name simple_adversary \
+        --num_agents 3 --num_landmarks 2 --n_rollout_threads 128 --num_mini_batch 1 --episode_length 25 \
+        --num_env_steps 2000000 --ppo_epoch 15 --gain 0.01 --lr 7e-4 --critic_lr 7e-4 --share_policy --use_device_env
 """
 import argparse
 import sys
 
 from onpolicy.config import get_config
+from onpolicy.envs.mpe.simple_adversary import TorchSimpleAdversary
 from onpolicy.envs.mpe.simple_push import TorchSimplePush
 from onpolicy.envs.mpe.simple_reference import TorchSimpleReference
 from onpolicy.envs.mpe.simple_speaker_listener import TorchSimpleSpeakerListener
@@ -63,9 +70,10 @@ from onpolicy.scripts.train import _launch
 # scenarios with an in-tree device implementation (--use_device_env; row f1): the worlds are held on the policy's device
 DEVICE_ENVS = {"simple_spread": TorchSimpleSpread, "simple_reference": TorchSimpleReference,
                "simple_speaker_listener": TorchSimpleSpeakerListener, "simple_push": TorchSimplePush,
-               "simple_tag": TorchSimpleTag, "simple_world_comm": TorchSimpleWorldComm}
+               "simple_tag": TorchSimpleTag, "simple_world_comm": TorchSimpleWorldComm,
+               "simple_adversary": TorchSimpleAdversary}
 # ... of which these run under the separated runner (one policy per agent: the agents' spaces differ), the rest under the shared
-SEPARATED_DEVICE_ENVS = ("simple_speaker_listener", "simple_push", "simple_tag", "simple_world_comm")
+SEPARATED_DEVICE_ENVS = ("simple_speaker_listener", "simple_push", "simple_tag", "simple_world_comm", "simple_adversary")
 TAG_DEFAULTS = (3, 1)       # adversaries, good agents where --num_adversaries / --num_good_agents are not given
 WORLD_COMM_DEFAULTS = (4, 2)    # ... of simple_world_comm: the reference's documented counts
 # the scenarios whose agents are adversaries followed by good agents
@@ -109,7 +117,7 @@ def parse_args(args, parser):
     parser.add_argument('--num_agents', type=int, default=2, help="number of players")
     parser.add_argument('--use_device_env', action='store_true', default=False,
                         help="simple_spread or simple_reference (shared-policy runner) or simple_speaker_listener, "
-                             "simple_push, simple_tag or simple_world_comm (separated runner: --share_policy) with the training worlds held as "
+                             "simple_push, simple_tag, simple_world_comm or simple_adversary (separated runner: --share_policy) with the training worlds held as "
                              "tensors on the policy's device: no per-step host round trip")
     # (argparse.SUPPRESS: the attribute exists only when the flag is given, so a default parse carries the reference's flags
     # and --use_device_env, nothing else; readers use getattr(args, "fused_multi_loss", False))
@@ -157,6 +165,10 @@ def main(args):
             raise NotImplementedError("--use_device_env: simple_push colours landmark l on channel l + 1 of three, so "
                                       "--num_landmarks is 1 or 2 (the reference fails at 3), not %d"
                                       % all_args.num_landmarks)
+        if scenario == "simple_adversary" and device.type != "cuda":
+            raise NotImplementedError("--use_device_env: simple_adversary steps through its HIP kernel alone (no "
+                                      "tensor-op route stands in for it in a run), so it needs a HIP device, not %s"
+                                      % device)
         if scenario in KIND_DEFAULTS:
             adv, good = tag_counts(all_args)
             if adv < 1 or good < 1 or all_args.num_agents != adv + good:

@@ -3,7 +3,8 @@
 128 rollout threads, hidden 64, one policy per agent) -- or, with ``--scenario simple_push --num_agents A --num_landmarks
 L``, of keep-away at the same script family's shape, or, with ``--scenario simple_tag --num_adversaries V
 --num_good_agents G --num_landmarks L``, of predator-prey, or, with ``--scenario simple_world_comm`` and the same three
-flags, of predator-prey with forests, food and a speaking leader -- on one MI355X with the worlds on the device (--use_device_env),
+flags, of predator-prey with forests, food and a speaking leader, or, with ``--scenario simple_adversary --num_agents A``,
+of physical deception (A - 1 landmarks whatever ``--num_landmarks`` says) -- on one MI355X with the worlds on the device (--use_device_env),
 timed two ways in the same process, alternating: the separated runner's eager device loop (collect -> envs.step ->
 insert: what MAPPO_ROLLOUT_GRAPH=0 runs) and the captured step (runner/separated/rollout_graph.py: one graph launch + one
 slab write per agent).  Both start every rollout from the buffers' row 0 and leave the same fields behind.
@@ -42,7 +43,7 @@ def summary(ms):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--scenario", default="simple_speaker_listener", choices=("simple_speaker_listener", "simple_push", "simple_tag", "simple_world_comm"))
+    ap.add_argument("--scenario", default="simple_speaker_listener", choices=("simple_speaker_listener", "simple_push", "simple_tag", "simple_world_comm", "simple_adversary"))
     ap.add_argument("--num_agents", type=int, default=2, help="simple_tag / simple_world_comm: --num_adversaries + --num_good_agents instead")
     ap.add_argument("--num_adversaries", type=int, default=3, help="simple_tag / simple_world_comm only")
     ap.add_argument("--num_good_agents", type=int, default=1, help="simple_tag / simple_world_comm only")
