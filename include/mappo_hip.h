@@ -880,6 +880,23 @@ int mappo_simple_push_step(double* pos, double* vel, double* landmarks, int64_t*
                            int64_t n_worlds, int num_agents, int num_landmarks, int world_length, int auto_reset,
                            mappo_stream_t stream);
 
+/* ---------------------------------------------------- K11 wide: simple_push worlds of up to 64 agents ----
+ * The step of mappo_simple_push_step -- its operands, its state updated in place, its outputs -- for A = num_agents in
+ * 2..MAPPO_ENV_WIDE_MAX_ENTITIES and L = num_landmarks in 1..2.  Where the thin kernel keeps a world in one thread's
+ * registers, here the lanes of a wave lie along a world's agents (32 lanes per world while A <= 32, else 64) and the
+ * agents' positions and velocities in LDS; the landmarks take no lanes: every lane of a world keeps both, and the
+ * goal's position, in registers.  The arithmetic is the thin kernel's in its order and the contact sum never leaves its
+ * lane; d_0 travels by a shuffle and the nearest good agent's distance is an fmin butterfly, so no floating sum is
+ * reordered against it.  A world's observation row has an odd number of floats whenever L = 2 and A is even, so it
+ * leaves as 4-byte stores that the world's lanes lay side by side along the whole row (obs needs no more than float
+ * alignment).  MAPPO_E_SHAPE for A < 2 or L < 1, MAPPO_E_TOO_MANY for A > 64 or L > 2; nothing is launched or written
+ * then. */
+int mappo_simple_push_step_wide(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,
+                                const int64_t* actions, const double* fresh_pos, const double* fresh_landmarks,
+                                const int64_t* fresh_goal, float* obs, float* rewards, uint8_t* dones,
+                                double* per_agent, int64_t n_worlds, int num_agents, int num_landmarks,
+                                int world_length, int auto_reset, mappo_stream_t stream);
+
 /* ----------------------------------------------------- K11 family: simple_adversary worlds on the device ----
  * One env step of `n_worlds` physical-deception worlds (reference onpolicy/envs/mpe/scenarios/simple_adversary.py,
  * environment.py:115-255, core.py:160-190 and :207-288; A = num_agents in 2..MAPPO_ENV_WIDE_MAX_ENTITIES, L =

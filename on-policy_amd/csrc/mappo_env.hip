@@ -800,6 +800,151 @@ __global__ void __launch_bounds__(kWideThreads) adversary_step_kernel(AdversaryA
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// simple_push past kMax agents (K11 wide for keep-away): the wide work split -- LPW lanes own a world, lane e its agent
+// e -- with push_step_kernel's arithmetic, expression by expression and in its order.  The landmarks take no lanes: the
+// palette caps them at two, so LPW follows from A alone, and every lane of a world keeps both of them, and the goal's
+// position, in registers (world-uniform loads); LDS holds the agents' positions and velocities and nothing else.  The
+// contact sum is the lane's own, over j ascending and read as broadcasts, so no floating sum is reordered against the
+// thin kernel; what crosses lanes is d_0, a shuffle from lane 0, and the nearest good agent's distance, an fmin
+// butterfly that the adversary, idle lanes and dead worlds feed +inf (a minimum does not depend on its order).
+//
+// The observation is ONE row per world of Da + (A - 1) Dg floats, and Dg = 7 + 5 L + 2 (A - 1) is odd with two
+// landmarks: every second good segment starts at an odd float, and the row itself is odd whenever A - 1 is, so every
+// second world's row is not 8-byte aligned and the (x, y) pairs of the other wide kernels have no aligned home.  The
+// world's lanes therefore walk the concatenated row float by float: lane k writes the elements k, k + LPW, ... as
+// 4-byte stores, 128 or 256 contiguous bytes per wave instruction, and decodes each flat index behind the adversary's
+// segment into (agent, column) with one integer division by Dg.
+template <int LPW>
+__global__ void __launch_bounds__(kWideThreads) push_step_wide_kernel(PushArgs a) {
+    static_assert(LPW == 32 || LPW == 64, "a world is half a wave or a whole one");
+    // one double2 per lane and array: the image of world slot k is [k * LPW, (k + 1) * LPW)
+    __shared__ double2 s_pos[kWideThreads], s_vel[kWideThreads];
+    const World& s = a.s;
+    const int A = a.A, L = a.L;
+    const int tid = threadIdx.x, lane = tid % LPW, base = tid - lane;
+    const long long w = (long long)blockIdx.x * (kWideThreads / LPW) + tid / LPW;
+    // no thread leaves before the last barrier: a world past n, and a lane past the world's agents, is predicated
+    const bool live = w < s.n, is_agent = live && lane < A;
+    const long long ia = w * A + lane;
+    double2 p = {0.0, 0.0}, v = {0.0, 0.0}, l0 = {0.0, 0.0}, l1 = {0.0, 0.0};
+    long long mv = 0, t = 0;
+    int goal = 0;
+    if (is_agent) {
+        p = reinterpret_cast<const double2*>(s.pos)[ia];
+        v = reinterpret_cast<const double2*>(s.vel)[ia];
+        mv = a.act[ia];
+    }
+    if (live) {
+        l0 = reinterpret_cast<const double2*>(s.land)[w * L];
+        if (L > 1) l1 = reinterpret_cast<const double2*>(s.land)[w * L + 1];
+        t = s.t[w] + 1;
+        goal = (int)a.goal[w];
+    }
+    s_pos[tid] = p;
+    __syncthreads();
+    // ---- forces: action + soft contacts (add_contact_forces for one agent), then integrate's expressions
+    if (is_agent) {
+        double fx, fy, sx = 0.0, sy = 0.0;
+        action_force(mv, fx, fy);
+        for (int j = 0; j < A; ++j) {
+            if (j == lane) continue;
+            const double2 o = s_pos[base + j];
+            contact_force(p.x - o.x, p.y - o.y, kPushSize + kPushSize, sx, sy);
+        }
+        fx += sx;
+        fy += sy;
+        v.x = v.x * (1 - kDamping) + fx * kDt;
+        v.y = v.y * (1 - kDamping) + fy * kDt;
+        p.x = p.x + v.x * kDt;
+        p.y = p.y + v.y * kDt;
+    }
+    // ---- reward (simple_push.py:66-82): every lane its distance to the goal; d_0 and the nearest good agent's cross
+    double gx = goal == 0 ? l0.x : l1.x, gy = goal == 0 ? l0.y : l1.y;
+    const double dx = p.x - gx, dy = p.y - gy;
+    const double d = sqrt(dx * dx + dy * dy);
+    const double own = __shfl(d, 0, LPW);                                          // the adversary's
+    const double nearest = world_min<LPW>(is_agent && lane > 0 ? d : HUGE_VAL);
+    // ---- outcome and restart (write_outcome with each agent's own reward, restart_from_fresh, store_world for one agent)
+    const bool done = t >= s.world_length, restart = done && s.auto_reset;
+    if (is_agent) {
+        const double pa = lane == 0 ? nearest - own : -d;
+        s.per_agent[ia] = pa;
+        s.rew[ia] = (float)pa;
+        s.done[ia] = done ? 1 : 0;
+        if (restart) {
+            p = reinterpret_cast<const double2*>(s.fresh_pos)[ia];
+            v = double2{0.0, 0.0};
+        }
+        reinterpret_cast<double2*>(s.pos)[ia] = p;
+        reinterpret_cast<double2*>(s.vel)[ia] = v;
+    }
+    if (live && restart) {
+        // every lane takes the new landmarks and the new goal into its registers; lanes 0 and 1 store a landmark each
+        l0 = reinterpret_cast<const double2*>(s.fresh_land)[w * L];
+        l0 = double2{kPushLandmarkScale * l0.x, kPushLandmarkScale * l0.y};
+        if (L > 1) {
+            l1 = reinterpret_cast<const double2*>(s.fresh_land)[w * L + 1];
+            l1 = double2{kPushLandmarkScale * l1.x, kPushLandmarkScale * l1.y};
+        }
+        // (selected by component: a choice between the two double2 would put them in an array, in scratch)
+        if (lane < L)
+            reinterpret_cast<double2*>(s.land)[w * L + lane] = double2{lane == 0 ? l0.x : l1.x, lane == 0 ? l0.y : l1.y};
+        goal = (int)a.fresh_goal[w];
+        gx = goal == 0 ? l0.x : l1.x;
+        gy = goal == 0 ? l0.y : l1.y;
+    }
+    if (live && lane == 0) {
+        s.t[w] = restart ? 0 : t;
+        if (restart) a.goal[w] = goal;
+    }
+    __syncthreads();        // every lane has read the old positions
+    s_pos[tid] = p;
+    s_vel[tid] = v;
+    __syncthreads();
+    // ---- observation of the (possibly restarted) world (simple_push.py:84-104).  The adversary's columns: own velocity
+    // at 0, the landmarks relative to it at 2, the other agents from 2 + 2 L.  A good agent's: own velocity at 0, the goal
+    // relative to it at 2, its colour at 4 (0.75 on the goal's channel), the landmarks relative to it at 7, their colours
+    // from 7 + 2 L (0.9 on a landmark's own channel), the other agents from 7 + 5 L.  Values are formed in float64 and
+    // converted once
+    const int Da = 2 + 2 * L + 2 * (A - 1), Dg = 7 + 5 * L + 2 * (A - 1);
+    const int width = Da + (A - 1) * Dg, count = live ? width : 0;
+    float* row = s.obs + w * (long long)width;
+    for (int q = lane; q < count; q += LPW) {
+        int i = 0, c = q;
+        if (q >= Da) {
+            const int g = (q - Da) / Dg;
+            i = 1 + g;
+            c = q - Da - g * Dg;
+        }
+        const int at_land = i > 0 ? 7 : 2, at_other = at_land + (i > 0 ? 5 : 2) * L;
+        const double2 me = s_pos[base + i];
+        float o;
+        if (c < 2) {
+            const double2 e = s_vel[base + i];
+            o = (float)(c == 0 ? e.x : e.y);
+        } else if (c < 4 && i > 0) {
+            o = (float)(c == 2 ? gx - me.x : gy - me.y);
+        } else if (c < at_land) {
+            o = c - 5 == goal ? 0.75f : 0.25f;
+        } else if (c < at_land + 2 * L) {
+            const int k = c - at_land;
+            const double ex = k < 2 ? l0.x : l1.x, ey = k < 2 ? l0.y : l1.y;
+            o = (float)(k & 1 ? ey - me.y : ex - me.x);
+        } else if (c < at_other) {
+            const int k = c - at_land - 2 * L, lm = k >= 3;
+            o = k - 3 * lm == lm + 1 ? 0.9f : 0.1f;
+        } else {
+            const int k = c - at_other;
+            int j = k >> 1;
+            j += j >= i;
+            const double2 e = s_pos[base + j];
+            o = (float)(k & 1 ? e.y - me.y : e.x - me.x);
+        }
+        row[q] = o;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // simple_tag (predator-prey; scenarios/simple_tag.py): agents 0..Nadv-1, the adversaries, chase the good agents Nadv..A-1
 // among landmarks that collide and never move.  An adversary is large and slow, a good agent small and fast; every agent
 // moves, is silent, collides and has a top speed.  Not collaborative: each agent is paid its own reward.  No state besides
@@ -1544,6 +1689,25 @@ extern "C" int mappo_simple_push_step(double* pos, double* vel, double* landmark
                   n_worlds, world_length, auto_reset};
     return launch_step(push_step_kernel, PushArgs{s, i64(goal), i64(actions), i64(fresh_goal), num_agents, num_landmarks},
                        stream_);
+}
+
+extern "C" int mappo_simple_push_step_wide(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,
+                                           const int64_t* actions, const double* fresh_pos,
+                                           const double* fresh_landmarks, const int64_t* fresh_goal, float* obs,
+                                           float* rewards, uint8_t* dones, double* per_agent, int64_t n_worlds,
+                                           int num_agents, int num_landmarks, int world_length, int auto_reset,
+                                           mappo_stream_t stream_) {
+    if (!pos || !vel || !landmarks || !t || !goal || !actions || !obs || !rewards || !dones || !per_agent)
+        return MAPPO_E_NULL;
+    if (auto_reset && (!fresh_pos || !fresh_landmarks || !fresh_goal)) return MAPPO_E_NULL;
+    if (n_worlds <= 0 || num_agents < 2 || num_landmarks < 1 || world_length < 1) return MAPPO_E_SHAPE;
+    if (num_agents > kWideMax || num_landmarks > kPushLandmarks) return MAPPO_E_TOO_MANY;
+    const World s{pos, vel, landmarks, i64(t), fresh_pos, fresh_landmarks, obs, rewards, dones, per_agent,
+                  n_worlds, world_length, auto_reset};
+    const PushArgs a{s, i64(goal), i64(actions), i64(fresh_goal), num_agents, num_landmarks};
+    // the landmarks take no lanes: two worlds to a wave where the agents fit half of one
+    return num_agents <= 32 ? launch_wide<32>(push_step_wide_kernel<32>, a, stream_)
+                            : launch_wide<64>(push_step_wide_kernel<64>, a, stream_);
 }
 
 extern "C" int mappo_simple_adversary_step(double* pos, double* vel, double* landmarks, int64_t* t, int64_t* goal,

@@ -230,6 +230,7 @@ SIGNATURES = {
     "mappo_simple_reference_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
     "mappo_simple_speaker_listener_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),
     "mappo_simple_push_step": (_int, [_vp] * 13 + [_i64, _int, _int, _int, _int, _vp]),
+    "mappo_simple_push_step_wide": (_int, [_vp] * 13 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_adversary_step": (_int, [_vp] * 13 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_tag_step": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _int, _vp]),
     "mappo_simple_tag_step_wide": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _int, _vp]),

@@ -21,6 +21,8 @@ the adversary.
 The scenario never sets ``world.world_length``, so the reference ends an episode after 25 steps (core.py:137) whatever
 ``--episode_length`` says; so do these worlds.
 """
+import os
+
 from onpolicy.envs.mpe.particle_worlds import TorchParticleWorlds
 from onpolicy.envs.spaces import Discrete
 
@@ -29,6 +31,8 @@ _ADVERSARY = 0
 _AGENT_SIZE = 0.05
 _WORLD_LENGTH = 25          # core.py:137; simple_push.py leaves it alone
 _MAX_LANDMARKS = 2          # landmark l is coloured on channel l + 1 of three (simple_push.py:43-45)
+KERNEL_MAX_AGENTS = 16      # MAPPO_ENV_MAX_ENTITIES
+WIDE_MAX = 64               # MAPPO_ENV_WIDE_MAX_ENTITIES
 
 
 class TorchSimplePush(TorchParticleWorlds):
@@ -39,16 +43,20 @@ class TorchSimplePush(TorchParticleWorlds):
     one-hots, [N, A, 5] or concatenated [N, 5 A].  ``step`` returns obs [N, sum(obs_dims)] float32, rewards [N, A, 1]
     float32 (each agent's own), dones [N, A] bool, infos (lazy).  ``episode_length`` is accepted for the common call
     shape and unused: worlds report done at ``world_length`` steps (None: the reference's 25).  Kernel path:
-    ``mappo_simple_push_step`` (K11 family), up to 16 agents; more take the tensor-op path."""
+    ``mappo_simple_push_step`` (K11 family), up to 16 agents; more take the tensor-op path.  ``wide=True`` (None:
+    ``MAPPO_PUSH_WIDE=1`` in the environment when the worlds are built) opts into K11 wide
+    (``mappo_simple_push_step_wide``: the lanes of a wave along a world's agents) for every shape up to 64 agents; worlds
+    on the CPU step as tensor operations either way."""
     state_names = TorchParticleWorlds.state_names + ("goal",)
     landmark_scale = 0.8
     shared_reward = False
 
     def __init__(self, n_threads, num_agents=2, num_landmarks=2, episode_length=25, seed=1, auto_reset=True,
-                 device="cpu", world_length=None):
+                 device="cpu", world_length=None, wide=None):
         a, l = int(num_agents), int(num_landmarks)
         assert a >= 2, "simple_push: one adversary and at least one good agent"
         assert 1 <= l <= _MAX_LANDMARKS, "simple_push: the landmark palette has %d colours" % _MAX_LANDMARKS
+        self._wide = os.environ.get("MAPPO_PUSH_WIDE") == "1" if wide is None else bool(wide)
         dims = (2 + 2 * l + 2 * (a - 1),) + (7 + 5 * l + 2 * (a - 1),) * (a - 1)
         super().__init__(n_threads, a, l, _WORLD_LENGTH if world_length is None else world_length, seed, auto_reset,
                          device, obs_dim=dims, action_space=lambda: Discrete(_MOVES))
@@ -71,7 +79,7 @@ class TorchSimplePush(TorchParticleWorlds):
 
     @property
     def graph_safe(self):
-        return self.device.type == "cuda" and self.a <= 16
+        return self.device.type == "cuda" and self.a <= (WIDE_MAX if self._wide else KERNEL_MAX_AGENTS)
 
     def _fresh(self):
         """Agent positions U(-1, 1), landmarks U(-1, 1), the goal."""
@@ -121,7 +129,8 @@ class TorchSimplePush(TorchParticleWorlds):
         from onpolicy import _native
         p = _native.ptr
         fresh_pos, fresh_land, fresh_goal = fresh or (None, None, None)
-        _native.check(_native.lib().mappo_simple_push_step(
+        name = "mappo_simple_push_step_wide" if self._wide else "mappo_simple_push_step"
+        _native.check(getattr(_native.lib(), name)(
             p(self.pos), p(self.vel), p(self.landmarks), p(self.t), p(self.goal), p(idx), p(fresh_pos), p(fresh_land),
             p(fresh_goal), p(obs), p(rewards), p(dones), p(per_agent), self.n, self.a, self.l, self.world_length,
-            int(self.auto_reset), _native.stream_of(self.device)), "mappo_simple_push_step")
+            int(self.auto_reset), _native.stream_of(self.device)), name)

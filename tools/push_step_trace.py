@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Steps device-resident simple_push worlds through their kernel path (``mappo_simple_push_step``, one launch per step)
+"""Steps device-resident simple_push worlds through their kernel path (``mappo_simple_push_step``, one launch per step;
+``mappo_simple_push_step_wide``, up to 64 agents, with ``MAPPO_PUSH_WIDE=1`` in the environment)
 -- or, with ``--scenario simple_tag --num_adversaries V``, simple_tag worlds through ``mappo_simple_tag_step`` (through
 ``mappo_simple_tag_step_wide``, up to 64 agents and landmarks, with ``MAPPO_TAG_WIDE=1`` in the environment), or, with
 ``--scenario simple_world_comm --num_adversaries V``, simple_world_comm worlds (``--num_landmarks`` obstacles) through
