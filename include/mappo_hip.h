@@ -793,6 +793,56 @@ int64_t mappo_linear512_wgrad_workspace_floats(int K);
 int     mappo_linear512_wgrad(const float* dy, const float* x, int64_t rows, int K, int ldx, float* dw, float* workspace,
                               mappo_stream_t stream);
 
+/* --------------------------------------------------------------- K19: grouped forward-and-sample ----
+ * One launch evaluates G networks (1 <= G <= MAPPO_GROUPED_MAX_NETS) of K9's architecture -- the reference's MLPBase at
+ * hidden size 64 plus one output Linear (mlp.py:33-58; distributions.py:55-68 / r_actor_critic.py:147-175) -- on the same
+ * `rows` rows: every actor and critic of a separated-runner step (reference runner/separated/mpe_runner.py:94-120), each
+ * with its own weights on its own column slice of the env's joint observation row.  Per network (all pointers float32
+ * device memory, 4-byte aligned; nothing needs more):
+ *   src, ld, col, din   the input is columns col .. col + din - 1 of a matrix whose rows are ld floats apart
+ *                       (1 <= din <= MAPPO_GROUPED_MAX_DIN, col >= 0, col + din <= ld; any offset, any width)
+ *   in_g, in_b [din]    the input LayerNorm's weight and bias, or both NULL (use_feature_normalization = False)
+ *   w1 [64, din], bias / ln_g / ln_b [l] [64], w2[l - 1] [64, 64], n_layers = 1 + layer_N in {2, 3}, act (1 Tanh, 2 ReLU),
+ *   ln_eps (every LayerNorm's), hidden (must be 64): as in mappo_mlp_t
+ *   wh [out, 64], bh [out], 1 <= out <= MAPPO_GROUPED_MAX_OUT: the output Linear
+ *   y [rows, out]       receives the head's output: required for a critic (noise == NULL), optional for an actor
+ *   noise [rows, out]   caller-drawn Exponential(1) noise: the network is a Discrete actor, and actions [rows] int64 /
+ *   actions, logp       logp [rows] float32 receive what mappo_categorical_sample gives on y with that noise (the same
+ *                       device function: the same bits)
+ * mappo_grouped_prepare checks every descriptor and copies them to `table` (device memory, mappo_grouped_table_bytes(G)
+ * bytes, 8-byte aligned) with a synchronous copy: once per set of networks -- the launch reads parameters through the
+ * pointers, so in-place optimiser steps need no new table.  mappo_grouped_forward enqueues exactly one kernel on `stream`
+ * (capturable) for the first G descriptors of a prepared table.  Products are plain float32 on the 32x32x2 matrix
+ * instruction.  Refused before anything is copied or enqueued: MAPPO_E_NULL (a missing pointer; one of in_g / in_b or of
+ * noise / actions / logp without the others; a critic without y), MAPPO_E_SHAPE (G, rows, din, col / ld, out, n_layers,
+ * hidden, ln_eps <= 0), MAPPO_E_FLAGS (act), MAPPO_E_ALIGN. */
+#define MAPPO_GROUPED_MAX_NETS 128
+#define MAPPO_GROUPED_MAX_DIN  16384
+#define MAPPO_GROUPED_MAX_OUT  32
+typedef struct mappo_grouped_net {
+    const float* src;
+    int64_t ld;
+    int32_t col, din, n_layers, act, out, hidden;
+    float ln_eps;
+    int32_t reserved;
+    const float* in_g;
+    const float* in_b;
+    const float* w1;
+    const float* bias[MAPPO_MLP_MAX_LAYERS];
+    const float* ln_g[MAPPO_MLP_MAX_LAYERS];
+    const float* ln_b[MAPPO_MLP_MAX_LAYERS];
+    const float* w2[MAPPO_MLP_MAX_LAYERS - 1];
+    const float* wh;
+    const float* bh;
+    float* y;
+    const float* noise;
+    int64_t* actions;
+    float* logp;
+} mappo_grouped_net_t;
+int64_t mappo_grouped_table_bytes(int G);
+int     mappo_grouped_prepare(const mappo_grouped_net_t* nets, int G, void* table);
+int     mappo_grouped_forward(const void* table, int G, int64_t rows, mappo_stream_t stream);
+
 /* --------------------------------------------------------------- K11: simple_spread worlds on the device ----
  * One env step of `n_worlds` cooperative-navigation worlds (the env of BASELINE.json configs[0] / configs[2]; reference
  * onpolicy/envs/mpe/core.py:120-190, environment.py:100-180, scenarios/simple_spread.py:60-103) as one launch, so that

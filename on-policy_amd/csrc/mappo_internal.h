@@ -76,5 +76,42 @@ __device__ __forceinline__ unsigned source_row(const RowMap& m, unsigned first_o
 int gather_standardize(const float* src, float* dst, int width, long long rows_out, const RowMap& map,
                        unsigned first_only, float eps, hipStream_t stream);
 
+// ---- K14's per-row body, shared by the sampling kernels of mappo_loss.hip and the grouped rollout kernel (K19)
+// Logit i of a head as the distribution sees it: -1e10 where the action is unavailable (distributions.py:64-67).
+__device__ __forceinline__ float masked_logit(const float* lg, const float* av, int i) {
+    return (av && av[i] == 0.f) ? -1e10f : lg[i];
+}
+
+// One head of one row: the normalised logits of `lg[0..na)` (entries whose availability is 0 count as -1e10), the sampled
+// action argmax_i p_i / q_i and its log-probability.
+__device__ __forceinline__ void sample_head(const float* lg, const float* av, const float* q, int na, long long* action,
+                                            float* logp) {
+    float mx = -INFINITY;
+    for (int i = 0; i < na; ++i) {
+        const float x = masked_logit(lg, av, i);
+        mx = fmaxf(mx, x);
+    }
+    float se = 0.f;
+    for (int i = 0; i < na; ++i) {
+        const float x = masked_logit(lg, av, i);
+        se += expf(x - mx);
+    }
+    const float lse = mx + logf(se);
+    int best = 0;
+    float best_v = -1.f, best_l = 0.f;
+    for (int i = 0; i < na; ++i) {
+        const float x = masked_logit(lg, av, i);
+        const float l = x - lse;                // normalised logit = log p_i
+        const float v = expf(l) / q[i];         // p_i / q_i (first maximum wins, like argmax)
+        if (v > best_v) {
+            best_v = v;
+            best = i;
+            best_l = l;
+        }
+    }
+    *action = best;
+    *logp = best_l;
+}
+
 }  // namespace mappo
 #endif

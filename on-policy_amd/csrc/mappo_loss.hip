@@ -441,41 +441,9 @@ extern "C" int mappo_ppo_loss_multi_f32(const mappo_ppo_loss_multi_t* args, mapp
 // drawn by the caller from torch's generator (graph-safe philox), so the distribution is exactly the framework's.
 // One thread per row; n_actions <= 64.
 
-// Logit i of a head as the distribution sees it: -1e10 where the action is unavailable (distributions.py:64-67).
-__device__ __forceinline__ float masked_logit(const float* lg, const float* av, int i) {
-    return (av && av[i] == 0.f) ? -1e10f : lg[i];
-}
-
-// One head of one row: the normalised logits of `lg[0..na)` (entries whose availability is 0 count as -1e10), the sampled
-// action argmax_i p_i / q_i and its log-probability.
-__device__ __forceinline__ void sample_head(const float* lg, const float* av, const float* q, int na, long long* action,
-                                            float* logp) {
-    float mx = -INFINITY;
-    for (int i = 0; i < na; ++i) {
-        const float x = masked_logit(lg, av, i);
-        mx = fmaxf(mx, x);
-    }
-    float se = 0.f;
-    for (int i = 0; i < na; ++i) {
-        const float x = masked_logit(lg, av, i);
-        se += expf(x - mx);
-    }
-    const float lse = mx + logf(se);
-    int best = 0;
-    float best_v = -1.f, best_l = 0.f;
-    for (int i = 0; i < na; ++i) {
-        const float x = masked_logit(lg, av, i);
-        const float l = x - lse;                // normalised logit = log p_i
-        const float v = expf(l) / q[i];         // p_i / q_i (first maximum wins, like argmax)
-        if (v > best_v) {
-            best_v = v;
-            best = i;
-            best_l = l;
-        }
-    }
-    *action = best;
-    *logp = best_l;
-}
+// (masked_logit / sample_head, the per-row body, live in mappo_internal.h: K19 samples with the same function)
+using mappo::masked_logit;
+using mappo::sample_head;
 
 __global__ void __launch_bounds__(256) categorical_sample_kernel(const float* logits, const float* avail, const float* noise,
                                                                  long long* actions, float* logp, long long rows, int na) {

@@ -218,6 +218,7 @@ int g_launch_error = 0;
 #include "mappo_mlp_impl.h"
 #include "mappo_gru_impl.h"
 #include "mappo_lin_impl.h"
+#include "mappo_grouped_impl.h"
 
 extern "C" int mappo_mlp_forward(const mappo_mlp_t* net, mappo_stream_t stream) {
     g_launch_error = 0;
@@ -298,4 +299,11 @@ extern "C" int mappo_linear512_wgrad(const float* dy, const float* x, int64_t ro
                                      float* workspace, mappo_stream_t stream) {
     g_launch_error = 0;
     return lin::wgrad(dy, x, rows, K, ldx, dw, workspace, static_cast<hipStream_t>(stream));
+}
+
+// ---- K19: every actor and critic of a separated-runner step in one launch (mappo_grouped_impl.h)
+extern "C" int64_t mappo_grouped_table_bytes(int G) { return G < 1 ? 0 : (int64_t)G * (int64_t)sizeof(mappo_grouped_net_t); }
+extern "C" int mappo_grouped_prepare(const mappo_grouped_net_t* nets, int G, void* table) { return grp::prepare(nets, G, table); }
+extern "C" int mappo_grouped_forward(const void* table, int G, int64_t rows, mappo_stream_t stream) {
+    return grp::forward(table, G, rows, static_cast<hipStream_t>(stream));
 }

@@ -106,6 +106,18 @@ class GRUSeq(ctypes.Structure):
                [("head_out", ctypes.c_int32), ("logits", _vp), ("dlogits", _vp), ("head_sums", ctypes.c_int32)]
 
 
+GROUPED_MAX_NETS, GROUPED_MAX_DIN, GROUPED_MAX_OUT = 128, 16384, 32     # MAPPO_GROUPED_MAX_*
+
+
+class GroupedNet(ctypes.Structure):
+    """struct mappo_grouped_net (include/mappo_hip.h): one network of a K19 launch."""
+    _fields_ = [("src", _vp), ("ld", _i64)] + \
+               [(n, ctypes.c_int32) for n in ("col", "din", "n_layers", "act", "out", "hidden")] + \
+               [("ln_eps", ctypes.c_float), ("reserved", ctypes.c_int32), ("in_g", _vp), ("in_b", _vp), ("w1", _vp),
+                ("bias", _vp * 3), ("ln_g", _vp * 3), ("ln_b", _vp * 3), ("w2", _vp * 2), ("wh", _vp), ("bh", _vp),
+                ("y", _vp), ("noise", _vp), ("actions", _vp), ("logp", _vp)]
+
+
 ADAM_MAX_TENSORS = 64
 
 
@@ -225,6 +237,10 @@ SIGNATURES = {
                                            _vp]),
     "mappo_linear512_wgrad_workspace_floats": (_i64, [_int]),
     "mappo_linear512_wgrad": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    # K19
+    "mappo_grouped_table_bytes": (_i64, [_int]),
+    "mappo_grouped_prepare": (_int, [ctypes.POINTER(GroupedNet), _int, _vp]),
+    "mappo_grouped_forward": (_int, [_vp, _int, _i64, _vp]),
     "mappo_simple_spread_step": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_spread_step_wide": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_reference_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),

@@ -46,6 +46,10 @@ def _joint_obs(obs):
 class MPERunner(Runner):
     def __init__(self, config):
         super(MPERunner, self).__init__(config)
+        # MAPPO_GROUPED_ROLLOUT=1 (read here): the eager device loop's collect() runs all agents' networks and sampling as
+        # one K19 launch, like the captured step (built at the first collect; False = the per-agent loop)
+        from onpolicy.algorithms.utils import grouped_rollout
+        self._grouped = None if grouped_rollout.enabled() and self._on_device else False
 
     def run(self):
         self.warmup()
@@ -126,6 +130,23 @@ class MPERunner(Runner):
         """-> per-agent lists of device tensors (values, actions, log-probs, RNN states) and the
         [envs][agents] one-hot actions for the envs (device-resident worlds: the integer actions [N, A] as they are)."""
         values, actions, action_log_probs, rnn_states, rnn_states_critic, one_hot = [], [], [], [], [], []
+        if self._grouped is None:
+            from onpolicy.algorithms.utils import grouped_rollout
+            b = self.buffer[0]
+            self._joint = torch.empty((self.n_rollout_threads, sum(getattr(self.envs, "obs_dims", ()))),
+                                      dtype=torch.float32, device=b.device)
+            self._grouped = grouped_rollout.build(self.policy, self.envs, self._joint, self.use_centralized_V) or False
+        if self._grouped:
+            # the joint row of this step from the buffers (whole under a centralised critic, else the agents' columns)
+            if self.use_centralized_V:
+                self._joint.copy_(self.buffer[0].share_obs[step])
+            for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
+                tr.prep_rollout()
+                if not self.use_centralized_V:
+                    self.envs.agent_obs(self._joint, agent_id).copy_(b.obs[step])
+            values, actions, action_log_probs = self._grouped.forward()
+            return values, actions, action_log_probs, [b.rnn_states[step] for b in self.buffer], \
+                [b.rnn_states_critic[step] for b in self.buffer], torch.cat(actions, -1)
         for agent_id, (tr, b) in enumerate(zip(self.trainer, self.buffer)):
             tr.prep_rollout()
             value, action, action_log_prob, rnn_state, rnn_state_critic = tr.policy.get_actions(

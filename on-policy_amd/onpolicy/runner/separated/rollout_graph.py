@@ -13,9 +13,13 @@ The agents' branches are recorded on one stream, in agent order: the eager loop'
 
 Stays eager (``build`` returns None) where the shared step does, and under a PopArt value head: its ``update`` rebinds
 the head's parameters, and the static-head mechanism of the shared graph is not carried over to one head per agent.
+
+``MAPPO_GROUPED_ROLLOUT=1`` (read when the graph is built): the per-agent ``get_actions`` loop becomes one noise draw and one
+K19 launch for all agents' actors and critics (algorithms/utils/grouped_rollout.py), reading the carried joint row.
 """
 import torch
 
+from onpolicy.algorithms.utils import grouped_rollout
 from onpolicy.runner.shared import rollout_graph as shared
 
 
@@ -37,13 +41,24 @@ class SeparatedRolloutGraph(shared.RolloutGraph):
             self.cur_rnn_c = [b.rnn_states_critic[0] for b in bufs]
         # the centralised critics all read the joint observation: carried once
         self.cur_joint = torch.empty(bufs[0].share_obs.shape[1:], **f32) if runner.use_centralized_V else None
+        self.grouped = None
+        if grouped_rollout.enabled():       # K19 reads every network's columns of the joint row: carried in any case
+            joint = self.cur_joint if self.cur_joint is not None else \
+                torch.empty((self.N, sum(getattr(self.envs, "obs_dims", ()))), **f32)
+            # (this step hands its policies no available_actions, like the reference's: nothing to refuse on that account)
+            self.grouped = grouped_rollout.build([tr.policy for tr in runner.trainer], self.envs, joint,
+                                                 runner.use_centralized_V)
+            if self.grouped is not None:
+                self.cur_joint = joint
 
     @torch.no_grad()
     def _body(self):
         r, N = self.r, self.N
         agents = range(self.A)
         values, actions, logp, rnn_a, rnn_c = [], [], [], [], []
-        for i, tr in zip(agents, r.trainer):
+        if self.grouped is not None:        # all agents' networks and sampling: one draw, one launch (feed-forward only)
+            values, actions, logp = self.grouped.forward()
+        for i, tr in zip(agents, () if self.grouped is not None else r.trainer):
             share = self.cur_joint if r.use_centralized_V else self.cur_obs[i]
             v, a, lp, ha, hc = tr.policy.get_actions(share, self.cur_obs[i], self.cur_rnn_a[i], self.cur_rnn_c[i],
                                                      self.cur_masks[i])
@@ -51,7 +66,7 @@ class SeparatedRolloutGraph(shared.RolloutGraph):
         obs, rewards, dones, infos = self.envs.step(torch.cat(actions, -1))
         masks = torch.where(dones, 0.0, 1.0)                        # [N, A]: 0 where the episode ended (one launch)
         # the carried state of the next step; the slab writes take the static tensors as they are
-        if r.use_centralized_V:
+        if self.cur_joint is not None:
             self.cur_joint.copy_(obs)
         out = []
         for i in agents:
@@ -78,9 +93,13 @@ class SeparatedRolloutGraph(shared.RolloutGraph):
     def begin_episode(self):
         """Row 0 of every agent's buffer is the state the rollout starts from (warmup() / after_update() put it there)."""
         bufs = self.r.buffer
-        if self.cur_joint is not None:
+        if self.grouped is not None:
+            self.grouped.check_parameters()
+        if self.cur_joint is not None and self.r.use_centralized_V:
             self.cur_joint.copy_(bufs[0].share_obs[0])
         for i, b in enumerate(bufs):
+            if self.cur_joint is not None and not self.r.use_centralized_V:
+                self.envs.agent_obs(self.cur_joint, i).copy_(b.obs[0])
             self.cur_obs[i].copy_(b.obs[0])
             self.cur_masks[i].copy_(b.masks[0])
             if self.recurrent:

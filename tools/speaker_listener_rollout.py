@@ -21,6 +21,11 @@ in a device synchronise) over ``--reps`` rollouts after ``--warmup`` untimed one
 than that.  ``eager_launches_per_step``: kernels of one eager step, ``eager_device_activities_per_step``: kernels, copies
 and memsets together, both counted by the framework's profiler in a run of its own after the timing (null with the reason
 where the profiler is not available).  Prints one JSON line.
+
+``--grouped`` adds a third way to the same alternation: the captured step of the grouped route (MAPPO_GROUPED_ROLLOUT=1: all
+agents' networks and sampling as one K19 launch), captured from the same runner after the default one.  ``grouped`` holds
+its times, ``spread_ms`` then covers all three ways, ``grouped_beats_graph`` says whether its median is below the default
+captured step's by more than that, and ``grouped_eager_launches_per_step`` counts the kernels of one eager step of the route.
 """
 import argparse
 import json
@@ -54,6 +59,7 @@ if __name__ == "__main__":
     ap.add_argument("--algorithm_name", default="rmappo")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--grouped", action="store_true", help="also time the captured step of the grouped route (K19)")
     ap.add_argument("--commit", default=None, help="commit the measurement was made on (recorded in the JSON line)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--append", action="store_true", help="add the JSON line to --out (one line per shape) instead of replacing it")
@@ -81,6 +87,12 @@ if __name__ == "__main__":
     assert graph is not None and graph.graph is not None, "the rollout step was not captured"
     for tr in runner.trainer:
         tr.prep_rollout()
+    grouped_graph = None
+    if opt.grouped:         # the same runner's step once more, captured with the route on
+        from onpolicy.runner.separated import rollout_graph
+        os.environ["MAPPO_GROUPED_ROLLOUT"] = "1"
+        grouped_graph = rollout_graph.build(runner)
+        assert grouped_graph is not None and grouped_graph.grouped is not None, "the grouped step was not captured"
 
     def eager_step(step):
         values, actions, logp, rnn_a, rnn_c, actions_env = runner.collect(step)
@@ -91,10 +103,13 @@ if __name__ == "__main__":
         for step in range(T):
             eager_step(step)
 
-    def graphed():
-        graph.begin_episode()
+    def graphed(g=graph):
+        g.begin_episode()
         for step in range(T):
-            graph.step()
+            g.step()
+
+    def grouped():
+        graphed(grouped_graph)
 
     def timed(rollout):
         torch.cuda.synchronize()
@@ -106,15 +121,20 @@ if __name__ == "__main__":
             b.after_update()
         return ms
 
+    ways = {"eager": eager, "graph": graphed}
+    if opt.grouped:
+        ways["grouped"] = grouped
     for _ in range(opt.warmup):
-        timed(eager), timed(graphed)
-    times = {"eager": [], "graph": []}
-    for _ in range(opt.reps):               # alternating: both ways see the same machine
-        times["eager"].append(timed(eager))
-        times["graph"].append(timed(graphed))
-    e, g = summary(times["eager"]), summary(times["graph"])
+        for way in ways.values():
+            timed(way)
+    times = {name: [] for name in ways}
+    for _ in range(opt.reps):               # alternating: all ways see the same machine
+        for name, way in ways.items():
+            times[name].append(timed(way))
+    sums = {name: summary(ms) for name, ms in times.items()}
+    e, g = sums["eager"], sums["graph"]
     launches, activities, why = None, None, None
-    spread = max(e["p90_ms"] - e["p10_ms"], g["p90_ms"] - g["p10_ms"])
+    spread = max(v["p90_ms"] - v["p10_ms"] for v in sums.values())
 
     agents = ("%d agents" % opt.num_agents if not by_kind else
               "%d adversaries against %d good agents" % (opt.num_adversaries, opt.num_good_agents))
@@ -133,6 +153,13 @@ if __name__ == "__main__":
            "eager_launches_note": "not counted",
            "graph_launches_per_step": "1 graph launch + %d slab writes (+ the integer actions' conversion per agent)"
                                       % len(runner.buffer)}
+    if opt.grouped:
+        k = sums["grouped"]
+        out.update({"grouped": k, "spread_is": "the largest of the ways' 10th-to-90th-percentile widths",
+                    "grouped_ms_per_env_step": round(k["median_ms"] / T, 4),
+                    "grouped_faster_than_graph_by_ms": round(g["median_ms"] - k["median_ms"], 4),
+                    "grouped_beats_graph": bool(g["median_ms"] - k["median_ms"] > spread),
+                    "grouped_eager_launches_per_step": None})
 
     kept = open(opt.out).read() if opt.out and opt.append and os.path.exists(opt.out) else ""
 
@@ -142,7 +169,8 @@ if __name__ == "__main__":
             with open(opt.out, "w") as f:
                 f.write(kept + json.dumps(out) + "\n")
     write()                                 # (the timings are on disk before the profiler starts)
-    try:                                    # in a run of its own: tracing slows the host
+    def count():
+        """-> (kernels, device activities) of one eager step, averaged over four."""
         from torch.profiler import ProfilerActivity, profile
         torch.cuda.synchronize()
         with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
@@ -151,10 +179,16 @@ if __name__ == "__main__":
             torch.cuda.synchronize()
         device = [ev for ev in prof.events() if str(ev.device_type).endswith("CUDA")]
         kernels = [ev for ev in device if not ev.name.lower().startswith(("memcpy", "memset"))]
-        if kernels:
-            launches, activities = len(kernels) / 4.0, len(device) / 4.0
-        else:
-            why = "the profiler recorded no kernel"
+        if not kernels:
+            raise RuntimeError("the profiler recorded no kernel")
+        return len(kernels) / 4.0, len(device) / 4.0
+
+    try:                                    # in a run of its own: tracing slows the host
+        launches, activities = count()
+        if opt.grouped:
+            runner._grouped = None          # the eager loop's collect() builds the route at its next call
+            eager_step(0)
+            out["grouped_eager_launches_per_step"] = count()[0]
     except Exception as exc:
         why = "%s: %s" % (type(exc).__name__, exc)
 
