@@ -843,6 +843,31 @@ int64_t mappo_grouped_table_bytes(int G);
 int     mappo_grouped_prepare(const mappo_grouped_net_t* nets, int G, void* table);
 int     mappo_grouped_forward(const void* table, int G, int64_t rows, mappo_stream_t stream);
 
+/* K19 recurrent: the same launch for recurrent policies (reference r_actor_critic.py with recurrent_N = 1, rnn.py:7-80):
+ * per network trunk -> GRU cell -> LayerNorm -> output Linear (-> sampling), with
+ *   x = trunk(columns), hm = h_in * mask (per row),
+ *   r = sigmoid(W_ir x + b_ir + W_hr hm + b_hr), z = sigmoid(W_iz x + b_iz + W_hz hm + b_hz),
+ *   n = tanh(W_in x + b_in + r * (W_hn hm + b_hn)), h' = (1 - z) * n + z * hm -> h_out (not normalised, as RNNLayer returns it),
+ *   y = head(LayerNorm(h'; rnn_g, rnn_b, net.ln_eps)) -> net.y, or sampled as above.
+ * `net` is the feed-forward descriptor (trunk, head, outputs) with its rules and limits; all other pointers are float32 device
+ * memory, 4-byte aligned.  Table, prepare and forward (one kernel, capturable) as above, with mappo_grouped_rnn_table_bytes(G)
+ * bytes.  Additionally refused: MAPPO_E_NULL (any of the nine pointers), MAPPO_E_SHAPE (h_out == h_in). */
+typedef struct mappo_grouped_rnn_net {
+    mappo_grouped_net_t net;
+    const float* h_in;
+    const float* mask;
+    float* h_out;
+    const float* w_ih;
+    const float* w_hh;
+    const float* b_ih;
+    const float* b_hh;
+    const float* rnn_g;
+    const float* rnn_b;
+} mappo_grouped_rnn_net_t;
+int64_t mappo_grouped_rnn_table_bytes(int G);
+int     mappo_grouped_rnn_prepare(const mappo_grouped_rnn_net_t* nets, int G, void* table);
+int     mappo_grouped_rnn_forward(const void* table, int G, int64_t rows, mappo_stream_t stream);
+
 /* --------------------------------------------------------------- K11: simple_spread worlds on the device ----
  * One env step of `n_worlds` cooperative-navigation worlds (the env of BASELINE.json configs[0] / configs[2]; reference
  * onpolicy/envs/mpe/core.py:120-190, environment.py:100-180, scenarios/simple_spread.py:60-103) as one launch, so that

@@ -85,16 +85,37 @@ __device__ __forceinline__ void tail(int act, const f32x16* acc, const float* ve
     else mlp::layer_tail<false, 2>(acc, vec, h, eps, hreg, nullptr, lane, mean, rstd);
 }
 
-__global__ void __launch_bounds__(kThreads) grouped_nets_kernel(const mappo_grouped_net_t* table, long long rows) {
-    __shared__ float r1[kTile];                     // first layer: the chunk tile; then partial tiles, weights, logits
-    __shared__ float r2[64 * kS];                   // the first hidden layer's weights; then head weights or logits
-    __shared__ __attribute__((aligned(16))) float vecs[3 * 192];   // per layer: bias | LayerNorm weight | bias
-    __shared__ float head_b[32], s_f[64], t_f[64], row_dm[32], row_rstd[32];
+// The shared arrays of a workgroup's trunk (declared by the kernel: the K19 kernels differ in what else they keep in LDS)
+struct Lds {
+    float* r1;                                      // [kTile] first layer: the chunk tile; then partial tiles, weights, logits
+    float* r2;                                      // [64 * kS] the first hidden layer's weights; then head weights or logits
+    float* vecs;                                    // [3 * 192], 16-byte aligned; per layer: bias | LayerNorm weight | bias
+    float *head_b, *s_f, *t_f, *row_dm, *row_rstd;  // [32], [64], [64], [32], [32]
+};
+// ... and a thread's place in its workgroup's tile
+struct Place {
+    int tid, lane, wave, c, h, out;                 // (wave: uniform; c, h: the row and half-wave of a lane; out = d->out)
+    long long row0;
+};
+__device__ __forceinline__ Place place_of(const mappo_grouped_net_t* d) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    return Place{tid, lane, prim::uniform(tid >> 6), lane & 31, lane >> 5, d->out, (long long)blockIdx.x * 32};
+}
 
-    const mappo_grouped_net_t* d = table + blockIdx.y;      // uniform: the descriptor is read with scalar loads
-    const int tid = threadIdx.x, lane = tid & 63, wave = prim::uniform(tid >> 6), c = lane & 31, h = lane >> 5;
-    const long long row0 = (long long)blockIdx.x * 32;
-    const int din = d->din, L = d->n_layers, out = d->out, act = d->act;
+// The trunk of network d on rows row0 .. row0 + 31: -> wave 0's hreg = the last block's LayerNorm output, 32 of its row's 64
+// features per lane (feature_of).  HEAD: the output Linear's weights are staged on the way ([32][kS] at head_w, the other
+// of r1 / r2 is `logits`); without it r1 and r2 are both free afterwards.  `early` runs on waves 1 .. 3 while wave 0 is in
+// the first hidden layer (after their share of the staging).  Ends behind a barrier.
+template <bool HEAD, class Early>
+__device__ __forceinline__ void trunk(const mappo_grouped_net_t* d, long long rows, const Lds& lds, const Place& at, float* hreg,
+                                      f32x16* acc, float*& head_w, float*& logits, Early early) {
+    float* r1 = lds.r1;
+    float* r2 = lds.r2;
+    float* vecs = lds.vecs;
+    float *head_b = lds.head_b, *s_f = lds.s_f, *t_f = lds.t_f, *row_dm = lds.row_dm, *row_rstd = lds.row_rstd;
+    const int tid = at.tid, lane = at.lane, wave = at.wave, c = at.c, h = at.h, out = at.out;
+    const long long row0 = at.row0;
+    const int din = d->din, L = d->n_layers, act = d->act;
     const float eps = d->ln_eps;
     const float* w1 = d->w1;
     const float* in_g = d->in_g;
@@ -102,7 +123,6 @@ __global__ void __launch_bounds__(kThreads) grouped_nets_kernel(const mappo_grou
     const bool in_ln = in_g != nullptr;
     float* xs = r1;
     float* ws = r1 + 32 * kS;
-
     for (int i = tid; i < L * 192; i += kThreads) {
         const int l = i / 192, j = i - 192 * l, part = j >> 6;
         const float* p = part == 0 ? d->bias[l] : part == 1 ? d->ln_g[l] : d->ln_b[l];
@@ -124,7 +144,6 @@ __global__ void __launch_bounds__(kThreads) grouped_nets_kernel(const mappo_grou
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) sacc[i] = tacc[i] = 0.f;
-    f32x16 acc[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -200,7 +219,6 @@ __global__ void __launch_bounds__(kThreads) grouped_nets_kernel(const mappo_grou
         }
     }
     __syncthreads();
-    float hreg[32];
     if (wave == 0) {
 #pragma unroll
         for (int s = 0; s < 32; ++s)
@@ -220,17 +238,18 @@ __global__ void __launch_bounds__(kThreads) grouped_nets_kernel(const mappo_grou
     // ---- hidden layers and head on wave 0; waves 1 .. 3 stage the weights of the step after
     if (wave != 0) {
         if (L == 3) stage_rows64(r1, d->w2[1], 64, 64, tid - 64, kThreads - 64);
-        else stage_rows64(r1, d->wh, 32, out, tid - 64, kThreads - 64);
+        else if (HEAD) stage_rows64(r1, d->wh, 32, out, tid - 64, kThreads - 64);
+        early();
     } else {
         dense64<2>(r2, c, h, hreg, acc);
         tail(act, acc, vecs + 192, h, eps, hreg, lane);
     }
     __syncthreads();
-    float* head_w = r1;
-    float* logits = r2;
+    head_w = r1;
+    logits = r2;
     if (L == 3) {
         if (wave != 0) {
-            stage_rows64(r2, d->wh, 32, out, tid - 64, kThreads - 64);
+            if (HEAD) stage_rows64(r2, d->wh, 32, out, tid - 64, kThreads - 64);
         } else {
             dense64<2>(r1, c, h, hreg, acc);
             tail(act, acc, vecs + 384, h, eps, hreg, lane);
@@ -239,6 +258,13 @@ __global__ void __launch_bounds__(kThreads) grouped_nets_kernel(const mappo_grou
         head_w = r2;
         logits = r1;
     }
+}
+
+// The head on wave 0's hreg (weights [32][kS] at head_w) -> the tile logits [32 rows][33]; then y, and an actor's sampling
+__device__ __forceinline__ void head_and_sample(const mappo_grouped_net_t* d, long long rows, const Place& at, const float* head_w,
+                                                float* logits, const float* head_b, const float* hreg, f32x16* acc) {
+    const int tid = at.tid, wave = at.wave, c = at.c, h = at.h, out = at.out;
+    const long long row0 = at.row0;
     if (wave == 0) {
         dense64<1>(head_w, c, h, hreg, acc);        // D[output (v & 3) + 8 (v >> 2) + 4 h][row c]
 #pragma unroll
@@ -261,6 +287,175 @@ __global__ void __launch_bounds__(kThreads) grouped_nets_kernel(const mappo_grou
         mappo::sample_head(logits + tid * 33, nullptr, d->noise + r * out, out,
                            reinterpret_cast<long long*>(d->actions) + r, d->logp + r);
     }
+}
+
+__global__ void __launch_bounds__(kThreads) grouped_nets_kernel(const mappo_grouped_net_t* table, long long rows) {
+    __shared__ float r1[kTile];
+    __shared__ float r2[64 * kS];
+    __shared__ __attribute__((aligned(16))) float vecs[3 * 192];
+    __shared__ float head_b[32], s_f[64], t_f[64], row_dm[32], row_rstd[32];
+
+    const mappo_grouped_net_t* d = table + blockIdx.y;      // uniform: the descriptor is read with scalar loads
+    const Lds lds = {r1, r2, vecs, head_b, s_f, t_f, row_dm, row_rstd};
+    const Place at = place_of(d);
+    float hreg[32];
+    f32x16 acc[2];
+    float *head_w, *logits;
+    trunk<true>(d, rows, lds, at, hreg, acc, head_w, logits, [] {});
+    head_and_sample(d, rows, at, head_w, logits, head_b, hreg, acc);
+}
+
+// ---- K19 recurrent: trunk -> GRU cell (recurrent_N = 1, 64 -> 64) -> LayerNorm -> head (-> sampling), per network, one launch
+//
+// The cell's six 64 x 64 products are 384 matrix instructions on 32 rows, as many again as a three-layer trunk.  They are
+// laid out so that wave 0 -- the trunk's only worker after the first layer -- gets 96 of them:
+//
+//   hidden side   W_hh hm (hm = h_in * mask) needs nothing of the trunk.  Waves 1 and 2 take it, one per half of the 64
+//                 features: three accumulator tiles each (r | z | n of their 32 features, all 32 rows; the transposed
+//                 product of the trunk, D[feature][row]), 96 instructions, issued while wave 0 runs the trunk's first
+//                 hidden layer.  The tiles then wait in (accumulator) registers.
+//   input side    W_ih x starts behind the trunk's last tail: wave 0 puts x into an LDS tile, then waves 0 and 3 take a
+//                 half of the features each (96 instructions) and hand their three tiles over through LDS, in register
+//                 order: slot (gate, v) of lane l at [(gate, v)][l], so neither side's accesses conflict.
+//   gates         where the hidden side waits: a lane of waves 1 / 2 holds r, z, n of 16 features of one row, reads hm
+//                 from the tile the product read, and writes h' into the tile x came from.
+//   out           waves 1 .. 3 copy that tile to h_out in whole rows (256-byte runs) while wave 0 reads it back in the
+//                 trunk's register layout, normalises it (an in-lane sum and one exchange per moment, like layer_tail)
+//                 and runs the head and the sampling as above.
+//
+// Both weight matrices are staged in LDS [192][kS] by all four waves before the first layer (B operands k = 32 h + s: the
+// two half-waves of a read are 32 banks apart), W_ih too: its A operands are read 32 times per workgroup, and staging it
+// later, from the one idle wave, would take that wave longer than the trunk's hidden layers last.  With the trunk's tiles
+// that is 159 KB of the CU's 160: dynamic LDS, granted as for K12, one workgroup per CU -- what a latency-sized launch wants.
+// The head's weights are staged behind the trunk (r2), the input side's tiles and then the logits go to r1.
+constexpr int kRnnW = 192 * kS;                         // one staged GRU weight matrix
+constexpr int kRnnVec = 6 * 64;                         // b_ir + b_hr | b_iz + b_hz | b_in | b_hn | LayerNorm weight | bias
+constexpr int kRnnLds = 2 * kRnnW + 2 * 32 * kS + kRnnVec;      // floats: W_hh | W_ih | hm tile | x, then h' tile | vectors
+static_assert(6 * 16 * 64 <= kTile, "the input side's six tiles pass through r1");
+
+__global__ void __launch_bounds__(kThreads) grouped_rnn_nets_kernel(const mappo_grouped_rnn_net_t* table, long long rows) {
+    __shared__ float r1[kTile];
+    __shared__ float r2[64 * kS];
+    __shared__ __attribute__((aligned(16))) float vecs[3 * 192];
+    __shared__ float head_b[32], s_f[64], t_f[64], row_dm[32], row_rstd[32];
+    float* whh = prim::lds();
+    float* wih = whh + kRnnW;
+    float* hmt = wih + kRnnW;                       // [32 rows][kS]
+    float* xt = hmt + 32 * kS;                      // [32 rows][kS]
+    float* gvec = xt + 32 * kS;
+
+    const mappo_grouped_rnn_net_t* e = table + blockIdx.y;      // uniform, as above
+    const mappo_grouped_net_t* d = &e->net;
+    const Place at = place_of(d);
+    const int tid = at.tid, lane = at.lane, wave = at.wave, c = at.c, h = at.h;
+    const long long row0 = at.row0;
+    const long long left = rows - row0;             // > 0
+    const int valid = left < 32 ? (int)left : 32;
+
+    stage_rows64(whh, e->w_hh, 192, 192, tid, kThreads);
+    stage_rows64(wih, e->w_ih, 192, 192, tid, kThreads);
+    for (int i = tid; i < 32 * 64; i += kThreads) {
+        const int r = i >> 6, k = i & 63;
+        hmt[r * kS + k] = r < valid ? e->h_in[(row0 + r) * 64 + k] * e->mask[row0 + r] : 0.f;
+    }
+    for (int i = tid; i < kRnnVec; i += kThreads) {
+        const int part = i >> 6, f = i & 63;
+        gvec[i] = part < 2 ? e->b_ih[64 * part + f] + e->b_hh[64 * part + f]
+                           : part == 2 ? e->b_ih[128 + f] : part == 3 ? e->b_hh[128 + f] : part == 4 ? e->rnn_g[f] : e->rnn_b[f];
+    }
+
+    f32x16 gh[3];                                   // waves 1, 2: W_hh hm of gate g, features 32 (wave - 1) + ..., all rows
+#pragma unroll
+    for (int g = 0; g < 3; ++g)
+#pragma unroll
+        for (int v = 0; v < 16; ++v) gh[g][v] = 0.f;
+    const Lds lds = {r1, r2, vecs, head_b, s_f, t_f, row_dm, row_rstd};
+    float hreg[32];
+    f32x16 acc[3];
+    float *unused_w, *unused_l;
+    trunk<false>(d, rows, lds, at, hreg, acc, unused_w, unused_l, [&] {
+        if (wave != 3) {
+            const float* w = whh + (32 * (wave - 1) + c) * kS + 32 * h;
+            const float* b = hmt + c * kS + 32 * h;
+#pragma unroll
+            for (int s = 0; s < 32; ++s) {
+                const float bv = b[s];
+#pragma unroll
+                for (int g = 0; g < 3; ++g) gh[g] = prim::mfma32(w[64 * g * kS + s], bv, gh[g]);
+            }
+        }
+    });
+
+    // ---- x into its tile; the head's weights behind the trunk
+    if (wave == 0) {
+#pragma unroll
+        for (int s = 0; s < 32; ++s) xt[c * kS + feature_of(s) + 4 * h] = hreg[s];
+    } else {
+        stage_rows64(r2, d->wh, 32, at.out, tid - 64, kThreads - 64);
+    }
+    __syncthreads();
+    // ---- input side: wave 0 features 0 .. 31, wave 3 features 32 .. 63
+    if (wave == 0 || wave == 3) {
+        const int half = wave == 3;
+        const float* w = wih + (32 * half + c) * kS + 32 * h;
+        const float* b = xt + c * kS + 32 * h;
+#pragma unroll
+        for (int g = 0; g < 3; ++g)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[g][v] = 0.f;
+#pragma unroll
+        for (int s = 0; s < 32; ++s) {
+            const float bv = b[s];
+#pragma unroll
+            for (int g = 0; g < 3; ++g) acc[g] = prim::mfma32(w[64 * g * kS + s], bv, acc[g]);
+        }
+#pragma unroll
+        for (int g = 0; g < 3; ++g)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) r1[((3 * half + g) * 16 + v) * 64 + lane] = acc[g][v];
+    }
+    __syncthreads();
+    // ---- gates on waves 1, 2: slot v is feature 32 half + (v & 3) + 8 (v >> 2) + 4 h of row c
+    if (wave == 1 || wave == 2) {
+        const int half = wave - 1;
+#pragma unroll
+        for (int v = 0; v < 16; ++v) {
+            const int f = 32 * half + (v & 3) + 8 * (v >> 2) + 4 * h;
+            const float* gi = r1 + (3 * half * 16 + v) * 64 + lane;
+            const float hm = hmt[c * kS + f];
+            const float r = gru::sigmoid_fast(gi[0] + gh[0][v] + gvec[f]);
+            const float z = gru::sigmoid_fast(gi[16 * 64] + gh[1][v] + gvec[64 + f]);
+            const float n = mlp::fast_tanh(gi[32 * 64] + gvec[128 + f] + r * (gh[2][v] + gvec[192 + f]));
+            xt[c * kS + f] = (1.f - z) * n + z * hm;
+        }
+    }
+    __syncthreads();
+    // ---- h' out (waves 1 .. 3, whole rows); LayerNorm of it on wave 0, in the trunk's register layout
+    if (wave != 0) {
+        for (int i = tid - 64; i < valid * 64; i += kThreads - 64) e->h_out[row0 * 64 + i] = xt[(i >> 6) * kS + (i & 63)];
+    } else {
+        float sum = 0.f, var = 0.f;
+#pragma unroll
+        for (int s = 0; s < 32; ++s) {
+            hreg[s] = xt[c * kS + feature_of(s) + 4 * h];
+            sum += hreg[s];
+        }
+        sum += prim::xhalf(sum);
+        const float mean = sum * (1.f / 64.f);
+#pragma unroll
+        for (int s = 0; s < 32; ++s) {
+            hreg[s] -= mean;
+            var += hreg[s] * hreg[s];
+        }
+        var += prim::xhalf(var);
+        const float rstd = prim::rsq_fast(var * (1.f / 64.f) + d->ln_eps);
+#pragma unroll
+        for (int s = 0; s < 32; ++s) {
+            const int f = feature_of(s) + 4 * h;
+            hreg[s] = hreg[s] * rstd * gvec[256 + f] + gvec[320 + f];
+        }
+    }
+    head_and_sample(d, rows, at, r2, r1, head_b, hreg, acc);
 }
 
 inline bool ok4(const void* p) { return mappo::aligned_to(p, 4); }
@@ -302,6 +497,38 @@ inline int forward(const void* table, int G, long long rows, hipStream_t stream)
     hipLaunchKernelGGL(grouped_nets_kernel, dim3((unsigned)((rows + 31) / 32), (unsigned)G), dim3(kThreads), 0, stream,
                        static_cast<const mappo_grouped_net_t*>(table), rows);
     return (int)hipGetLastError();
+}
+
+// ... of one recurrent descriptor
+inline int check(const mappo_grouped_rnn_net_t& n) {
+    const int e = check(n.net);
+    if (e) return e;
+    const void* ptrs[] = {n.h_in, n.mask, n.h_out, n.w_ih, n.w_hh, n.b_ih, n.b_hh, n.rnn_g, n.rnn_b};
+    for (const void* p : ptrs)
+        if (!p) return MAPPO_E_NULL;
+    if (n.h_out == n.h_in) return MAPPO_E_SHAPE;    // the state before the step stays what the caller put there
+    for (const void* p : ptrs)
+        if (!ok4(p)) return MAPPO_E_ALIGN;
+    return 0;
+}
+
+inline int prepare(const mappo_grouped_rnn_net_t* nets, int G, void* table) {
+    if (!nets || !table) return MAPPO_E_NULL;
+    if (G < 1 || G > MAPPO_GROUPED_MAX_NETS) return MAPPO_E_SHAPE;
+    if (!mappo::aligned_to(table, 8)) return MAPPO_E_ALIGN;
+    for (int g = 0; g < G; ++g) {
+        const int e = check(nets[g]);
+        if (e) return e;
+    }
+    return (int)hipMemcpy(table, nets, (size_t)G * sizeof(mappo_grouped_rnn_net_t), hipMemcpyHostToDevice);
+}
+
+inline int forward_rnn(const void* table, int G, long long rows, hipStream_t stream) {
+    if (!table) return MAPPO_E_NULL;
+    if (G < 1 || G > MAPPO_GROUPED_MAX_NETS || rows < 1 || rows > INT32_MAX) return MAPPO_E_SHAPE;
+    MAPPO_LAUNCH(grouped_rnn_nets_kernel, dim3((unsigned)((rows + 31) / 32), (unsigned)G), dim3(kThreads),
+                 kRnnLds * sizeof(float), stream, static_cast<const mappo_grouped_rnn_net_t*>(table), rows);
+    return MAPPO_LAUNCH_ERROR();
 }
 
 }  // namespace grp

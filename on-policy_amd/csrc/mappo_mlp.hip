@@ -307,3 +307,10 @@ extern "C" int mappo_grouped_prepare(const mappo_grouped_net_t* nets, int G, voi
 extern "C" int mappo_grouped_forward(const void* table, int G, int64_t rows, mappo_stream_t stream) {
     return grp::forward(table, G, rows, static_cast<hipStream_t>(stream));
 }
+// ... and its recurrent form: trunk, GRU cell, LayerNorm, head and sampling of every network, RNN states in and out
+extern "C" int64_t mappo_grouped_rnn_table_bytes(int G) { return G < 1 ? 0 : (int64_t)G * (int64_t)sizeof(mappo_grouped_rnn_net_t); }
+extern "C" int mappo_grouped_rnn_prepare(const mappo_grouped_rnn_net_t* nets, int G, void* table) { return grp::prepare(nets, G, table); }
+extern "C" int mappo_grouped_rnn_forward(const void* table, int G, int64_t rows, mappo_stream_t stream) {
+    g_launch_error = 0;
+    return grp::forward_rnn(table, G, rows, static_cast<hipStream_t>(stream));
+}

@@ -118,6 +118,12 @@ class GroupedNet(ctypes.Structure):
                 ("y", _vp), ("noise", _vp), ("actions", _vp), ("logp", _vp)]
 
 
+class GroupedRnnNet(ctypes.Structure):
+    """struct mappo_grouped_rnn_net (include/mappo_hip.h): one network of a recurrent K19 launch."""
+    _fields_ = [("net", GroupedNet)] + [(n, _vp) for n in ("h_in", "mask", "h_out", "w_ih", "w_hh", "b_ih", "b_hh", "rnn_g",
+                                                           "rnn_b")]
+
+
 ADAM_MAX_TENSORS = 64
 
 
@@ -241,6 +247,9 @@ SIGNATURES = {
     "mappo_grouped_table_bytes": (_i64, [_int]),
     "mappo_grouped_prepare": (_int, [ctypes.POINTER(GroupedNet), _int, _vp]),
     "mappo_grouped_forward": (_int, [_vp, _int, _i64, _vp]),
+    "mappo_grouped_rnn_table_bytes": (_i64, [_int]),
+    "mappo_grouped_rnn_prepare": (_int, [ctypes.POINTER(GroupedRnnNet), _int, _vp]),
+    "mappo_grouped_rnn_forward": (_int, [_vp, _int, _i64, _vp]),
     "mappo_simple_spread_step": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_spread_step_wide": (_int, [_vp] * 11 + [_i64, _int, _int, _int, _int, _vp]),
     "mappo_simple_reference_step": (_int, [_vp] * 14 + [_i64, _int, _int, _vp]),

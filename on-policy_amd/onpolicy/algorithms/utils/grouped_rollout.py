@@ -9,6 +9,10 @@ Opt-in: ``MAPPO_GROUPED_ROLLOUT=1``, read where the rollout graph / the runner's
 one tensor for all agents instead of one draw per agent, so the route samples other trajectories than the per-agent
 route from the first step on (same distribution).  ``refusal`` names what the kernel does not take; the per-agent body
 runs then.
+
+``MAPPO_GROUPED_ROLLOUT_RNN=1`` on top of it (read at the same places) lets the route take recurrent policies too: the recurrent
+K19 kernel (``mappo_grouped_rnn_prepare`` / ``mappo_grouped_rnn_forward``) carries every network through trunk, GRU cell, the
+LayerNorm behind it, head and sampling, and reads and writes the RNN states.  Without it recurrent policies are refused.
 """
 import os
 
@@ -22,12 +26,29 @@ def enabled():
     return os.environ.get("MAPPO_GROUPED_ROLLOUT", "0") == "1"
 
 
+def rnn_enabled():
+    return enabled() and os.environ.get("MAPPO_GROUPED_ROLLOUT_RNN", "0") == "1"
+
+
 def _blocks(base):
     return [base.mlp.fc1] + list(base.mlp.fc2)
 
 
-def refusal(policies, available_actions=False):
-    """Why these policies stay on the per-agent route (None: K19 takes them)."""
+def _rnn_refusal(net, eps):
+    """Why the recurrent K19 kernel does not take this actor's or critic's RNNLayer (None: it does)."""
+    if net._recurrent_N != 1:
+        return "recurrent_N = %d" % net._recurrent_N
+    gru, norm = net.rnn.rnn, net.rnn.norm
+    if (gru.input_size, gru.hidden_size) != (fused_mlp.HIDDEN, fused_mlp.HIDDEN) or not gru.bias or gru.bidirectional:
+        return "a GRU that is not 64 -> 64 with biases"
+    if not norm.elementwise_affine or norm.bias is None or float(norm.eps) != eps:
+        return "an RNN LayerNorm without affine parameters or with another eps than the trunk's"
+    return None
+
+
+def refusal(policies, available_actions=False, recurrent=False):
+    """Why these policies stay on the per-agent route (None: K19 takes them).  ``recurrent``: the recurrent kernel may be
+    used -- policies whose actors and critics are ALL recurrent (one GRU layer 64 -> 64) are taken then."""
     from . import distributions
     if distributions.SAMPLING_RNG != "device":
         return "the host sampling mode draws on the CPU generator"
@@ -37,8 +58,10 @@ def refusal(policies, available_actions=False):
         return "%d agents: more networks than one launch takes" % len(policies)
     for po in policies:
         actor, critic = po.actor, po.critic
-        if actor._recurrent or critic._recurrent:
+        if (actor._recurrent or critic._recurrent) and not recurrent:
             return "recurrent policies"
+        if not (actor._recurrent == critic._recurrent == policies[0].actor._recurrent):
+            return "a mixed set of recurrent and feed-forward networks"
         if actor.act.action_type != "Discrete":
             return "a %s action space" % actor.act.action_type
         if type(critic.v_out).__name__ == "PopArt":
@@ -57,6 +80,10 @@ def refusal(policies, available_actions=False):
                     or blocks[0][0].weight.shape[1] > _native.GROUPED_MAX_DIN:
                 return "a head of more than %d outputs or an input wider than %d" % (_native.GROUPED_MAX_OUT,
                                                                                       _native.GROUPED_MAX_DIN)
+        for net in (actor, critic) if actor._recurrent else ():
+            why = _rnn_refusal(net, float(_blocks(net.base)[0][2].eps))
+            if why is not None:
+                return why
     p = policies[0].actor.base.mlp.fc1[0].weight
     if not p.is_cuda or p.dtype != torch.float32:
         return "parameters that are not float32 on a HIP device"
@@ -84,12 +111,26 @@ def _describe(d, base, head, joint, col):
     return params
 
 
+def _describe_rnn(e, net, h_in, mask, h_out):
+    """Fill the recurrent part of descriptor ``e`` for ``net`` (an actor or critic) -> its parameter tensors."""
+    gru, norm = net.rnn.rnn, net.rnn.norm
+    params = [gru.weight_ih_l0, gru.weight_hh_l0, gru.bias_ih_l0, gru.bias_hh_l0, norm.weight, norm.bias]
+    e.w_ih, e.w_hh, e.b_ih, e.b_hh, e.rnn_g, e.rnn_b = (t.data_ptr() for t in params)
+    e.h_in, e.mask, e.h_out = h_in.data_ptr(), mask.data_ptr(), h_out.data_ptr()
+    return params
+
+
 class GroupedRollout(object):
     """The prepared launch for ``policies`` (``refusal`` returned None) reading ``joint`` [N, sum(obs_dims)], a static
     contiguous float32 device tensor the caller refreshes before every ``forward``.  ``keep_logits``: the actors' head
-    outputs are written too (``logits``, per agent [N, n]); the rollout itself needs only actions and log-probabilities."""
+    outputs are written too (``logits``, per agent [N, n]); the rollout itself needs only actions and log-probabilities.
 
-    def __init__(self, policies, obs_dims, joint, centralized, keep_logits=False):
+    Recurrent policies (``refusal(..., recurrent=True)`` returned None): ``states`` = per-agent lists (h_a, h_c, masks) of
+    static contiguous float32 tensors [N, 1, 64], [N, 1, 64], [N, 1] the launch reads -- the caller's own (the captured
+    step's carried state) or, by default, tensors of this object the caller refreshes like ``joint``; ``new_h_a`` /
+    ``new_h_c`` receive the new states, and ``forward`` returns them too."""
+
+    def __init__(self, policies, obs_dims, joint, centralized, keep_logits=False, states=None):
         N, dev = int(joint.shape[0]), joint.device
         assert joint.dim() == 2 and joint.stride(1) == 1 and joint.shape[1] == sum(obs_dims) and len(obs_dims) == len(policies)
         self.rows, self.G = N, 2 * len(policies)
@@ -99,12 +140,20 @@ class GroupedRollout(object):
         self.actions = [torch.empty((N, 1), dtype=torch.int64, device=dev) for _ in policies]
         self.logp = [torch.empty((N, 1), dtype=torch.float32, device=dev) for _ in policies]
         self.logits = [torch.empty((N, n), dtype=torch.float32, device=dev) for n in sizes] if keep_logits else None
-        nets = (_native.GroupedNet * self.G)()
+        self.recurrent = bool(policies[0].actor._recurrent)
+        nets = ((_native.GroupedRnnNet if self.recurrent else _native.GroupedNet) * self.G)()
+        if self.recurrent:
+            state = lambda *shape: [torch.zeros((N,) + shape, dtype=torch.float32, device=dev) for _ in policies]
+            self.h_a, self.h_c, self.masks = states if states is not None else (state(1, 64), state(1, 64), state(1))
+            self.new_h_a, self.new_h_c = state(1, 64), state(1, 64)
+            for t, shape in [(t, (N, 1, 64)) for t in self.h_a + self.h_c] + [(t, (N, 1)) for t in self.masks]:
+                assert t.shape == shape and t.is_contiguous() and t.dtype == torch.float32 and t.device == dev
+        net_of = (lambda e: e.net) if self.recurrent else (lambda e: e)
         self._params = []
         lo = at = 0
         for i, (po, width, n) in enumerate(zip(policies, obs_dims, sizes)):
             # the critics, whose rows are the long ones, first: their workgroups start first
-            c, a = nets[i], nets[len(policies) + i]
+            c, a = net_of(nets[i]), net_of(nets[len(policies) + i])
             self._params += _describe(c, po.critic.base, po.critic.v_out, joint, 0 if centralized else lo)
             c.y = self.values[i].data_ptr()
             self._params += _describe(a, po.actor.base, po.actor.act.action_out.linear, joint, lo)
@@ -113,10 +162,15 @@ class GroupedRollout(object):
             a.actions, a.logp = self.actions[i].data_ptr(), self.logp[i].data_ptr()
             a.y = self.logits[i].data_ptr() if keep_logits else None
             lo, at = lo + width, at + N * n
+            if self.recurrent:
+                self._params += _describe_rnn(nets[i], po.critic, self.h_c[i], self.masks[i], self.new_h_c[i])
+                self._params += _describe_rnn(nets[len(policies) + i], po.actor, self.h_a[i], self.masks[i], self.new_h_a[i])
         self._where = [t.data_ptr() for t in self._params]
         lib = _native.lib()
-        self.table = torch.empty(int(lib.mappo_grouped_table_bytes(self.G)), dtype=torch.uint8, device=dev)
-        _native.check(lib.mappo_grouped_prepare(nets, self.G, self.table.data_ptr()), "mappo_grouped_prepare")
+        size, prepare = (lib.mappo_grouped_rnn_table_bytes, lib.mappo_grouped_rnn_prepare) if self.recurrent else \
+            (lib.mappo_grouped_table_bytes, lib.mappo_grouped_prepare)
+        self.table = torch.empty(int(size(self.G)), dtype=torch.uint8, device=dev)
+        _native.check(prepare(nets, self.G, self.table.data_ptr()), prepare.__name__)
 
     def check_parameters(self):
         """The table holds the parameters' addresses: an optimiser step in place keeps them, a rebound tensor does not."""
@@ -125,18 +179,24 @@ class GroupedRollout(object):
 
     @torch.no_grad()
     def forward(self):
-        """-> (values, actions, log-probs): per-agent lists of the static [N, 1] tensors, valid until the next call."""
+        """-> (values, actions, log-probs): per-agent lists of the static [N, 1] tensors, valid until the next call;
+        recurrent policies: -> (values, actions, log-probs, new_h_a, new_h_c)."""
         self.noise.exponential_(1.0)
+        if self.recurrent:
+            _native.check(_native.lib().mappo_grouped_rnn_forward(self.table.data_ptr(), self.G, self.rows,
+                                                                  _native.stream_of(self.table.device)),
+                          "mappo_grouped_rnn_forward")
+            return self.values, self.actions, self.logp, self.new_h_a, self.new_h_c
         _native.check(_native.lib().mappo_grouped_forward(self.table.data_ptr(), self.G, self.rows,
                                                           _native.stream_of(self.table.device)), "mappo_grouped_forward")
         return self.values, self.actions, self.logp
 
 
-def build(policies, envs, joint, centralized, available_actions=False):
-    """-> the GroupedRollout of a runner's policies on ``joint``, or None (with the reason printed once) where K19 does not
-    take them."""
-    why = refusal(policies, available_actions) if hasattr(envs, "obs_dims") else "worlds without obs_dims"
+def build(policies, envs, joint, centralized, available_actions=False, states=None):
+    """-> the GroupedRollout of a runner's policies on ``joint`` (recurrent ones: on ``states``, see there), or None (with
+    the reason printed once) where K19 does not take them."""
+    why = refusal(policies, available_actions, rnn_enabled()) if hasattr(envs, "obs_dims") else "worlds without obs_dims"
     if why is not None:
         print("grouped rollout: %s; the per-agent step runs" % why)
         return None
-    return GroupedRollout(policies, envs.obs_dims, joint, centralized)
+    return GroupedRollout(policies, envs.obs_dims, joint, centralized, states=states)

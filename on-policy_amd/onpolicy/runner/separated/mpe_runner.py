@@ -144,6 +144,13 @@ class MPERunner(Runner):
                 tr.prep_rollout()
                 if not self.use_centralized_V:
                     self.envs.agent_obs(self._joint, agent_id).copy_(b.obs[step])
+                if self._grouped.recurrent:     # ... and the states and masks the recurrent launch reads
+                    self._grouped.h_a[agent_id].copy_(b.rnn_states[step])
+                    self._grouped.h_c[agent_id].copy_(b.rnn_states_critic[step])
+                    self._grouped.masks[agent_id].copy_(b.masks[step])
+            if self._grouped.recurrent:
+                values, actions, action_log_probs, rnn_states, rnn_states_critic = self._grouped.forward()
+                return values, actions, action_log_probs, rnn_states, rnn_states_critic, torch.cat(actions, -1)
             values, actions, action_log_probs = self._grouped.forward()
             return values, actions, action_log_probs, [b.rnn_states[step] for b in self.buffer], \
                 [b.rnn_states_critic[step] for b in self.buffer], torch.cat(actions, -1)

@@ -15,7 +15,9 @@ Stays eager (``build`` returns None) where the shared step does, and under a Pop
 the head's parameters, and the static-head mechanism of the shared graph is not carried over to one head per agent.
 
 ``MAPPO_GROUPED_ROLLOUT=1`` (read when the graph is built): the per-agent ``get_actions`` loop becomes one noise draw and one
-K19 launch for all agents' actors and critics (algorithms/utils/grouped_rollout.py), reading the carried joint row.
+K19 launch for all agents' actors and critics (algorithms/utils/grouped_rollout.py), reading the carried joint row; with
+``MAPPO_GROUPED_ROLLOUT_RNN=1`` on top of it also for recurrent policies, whose launch reads the carried RNN states and masks in
+place and hands back the new states.
 """
 import torch
 
@@ -47,7 +49,8 @@ class SeparatedRolloutGraph(shared.RolloutGraph):
                 torch.empty((self.N, sum(getattr(self.envs, "obs_dims", ()))), **f32)
             # (this step hands its policies no available_actions, like the reference's: nothing to refuse on that account)
             self.grouped = grouped_rollout.build([tr.policy for tr in runner.trainer], self.envs, joint,
-                                                 runner.use_centralized_V)
+                                                 runner.use_centralized_V,
+                                                 states=(self.cur_rnn_a, self.cur_rnn_c, self.cur_masks))
             if self.grouped is not None:
                 self.cur_joint = joint
 
@@ -56,8 +59,8 @@ class SeparatedRolloutGraph(shared.RolloutGraph):
         r, N = self.r, self.N
         agents = range(self.A)
         values, actions, logp, rnn_a, rnn_c = [], [], [], [], []
-        if self.grouped is not None:        # all agents' networks and sampling: one draw, one launch (feed-forward only)
-            values, actions, logp = self.grouped.forward()
+        if self.grouped is not None:        # all agents' networks and sampling: one draw, one launch
+            values, actions, logp, rnn_a, rnn_c = (self.grouped.forward() + ([], []))[:5]
         for i, tr in zip(agents, () if self.grouped is not None else r.trainer):
             share = self.cur_joint if r.use_centralized_V else self.cur_obs[i]
             v, a, lp, ha, hc = tr.policy.get_actions(share, self.cur_obs[i], self.cur_rnn_a[i], self.cur_rnn_c[i],

@@ -91,6 +91,7 @@ if __name__ == "__main__":
     if opt.grouped:         # the same runner's step once more, captured with the route on
         from onpolicy.runner.separated import rollout_graph
         os.environ["MAPPO_GROUPED_ROLLOUT"] = "1"
+        os.environ["MAPPO_GROUPED_ROLLOUT_RNN"] = "1"       # (recurrent policies: the recurrent form of the launch)
         grouped_graph = rollout_graph.build(runner)
         assert grouped_graph is not None and grouped_graph.grouped is not None, "the grouped step was not captured"
 
